@@ -8,6 +8,15 @@ BASELINE.json config) with random-init weights.
 
 Usage:
   python bench.py [--gpus N] [--steps K] [--warmup W] [--engine fused|eager]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times exactly K steps and prints one JSON
+result line; `ms_per_step` is the wall time of one timed step.
+--dump-outputs DIR additionally writes what the last timed step produced
+(loss terms, reconstruction, and the trained parameters) as float32
+DIR/<name>.npy; inputs and weights are seeded, so equal arguments give
+comparable dumps across builds. --full is where measurements beyond the
+headline figure belong; the benchmark has none today, so it changes
+nothing yet.
 Multi-GPU (driver contract): launched under torch.distributed.run with
 one rank per GPU; ranks read RANK/LOCAL_RANK/WORLD_SIZE from the env.
 Weak scaling: each rank trains its own shard of day cross-sections
@@ -55,7 +64,36 @@ def parse_args():
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--n_days", type=int, default=32,
                    help="distinct synthetic day tensors cycled through")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                   default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's "
+                        "outputs and the trained parameters to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (none today; a plain run stays lean)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each named tensor as float32 out_dir/<name>.npy. The dump
+    stays under 64 MB in all: an array over its share is replaced by a
+    fixed seeded sample of its elements (same indices every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    max_elems = (64 << 20) // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > max_elems:
+            idx = np.random.default_rng(0).choice(a.size, max_elems,
+                                                  replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -156,7 +194,7 @@ def main():
             multi.runner()
     else:
         for i in range(args.steps):
-            step_fn(*days[(args.warmup + i) % len(days)])
+            last_loss = step_fn(*days[(args.warmup + i) % len(days)])
     barrier()
     sync()
     t1 = time.perf_counter()
@@ -209,6 +247,19 @@ def main():
             "engine": engine_name,
         },
     }
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step computed, plus the weights all timed
+        # steps trained (about 1 MB at the benchmark shapes)
+        with torch.no_grad():
+            arrays = {"params": torch.cat([p.reshape(-1)
+                                           for p in model.parameters()])}
+            if multi is not None:
+                w = trainer.ws
+                arrays.update(loss=w["loss"], mse=w["mse"], kl=w["kl"],
+                              recon=w["recon"])
+            else:
+                arrays["loss"] = last_loss.reshape(1)
+            dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         print(json.dumps(result))
     if is_distributed():

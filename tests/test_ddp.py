@@ -137,9 +137,14 @@ def _train_main_worker(rank, world_size, port, tmpdir, q):
 
 
 @pytest.mark.timeout(240)
-def test_train_main_two_rank_end_to_end(tmp_path):
+def test_train_main_two_rank_end_to_end(tmp_path, monkeypatch):
     """Full experiment driver on 2 gloo ranks: day sharding, loss
     all-reduce, rank-0 best-val checkpoint + optimizer side-car."""
+    # CPU/gloo ranks: the spawned workers must not see a GPU (rank r
+    # would select GPU r, which a 1-GPU machine does not have); an
+    # out-of-range index leaves no device visible to them
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "-1")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_train_main_worker,
@@ -148,12 +153,19 @@ def test_train_main_two_rank_end_to_end(tmp_path):
     for p in procs:
         p.start()
     results = {}
-    for _ in range(2):
-        rank, best, has_ckpt, has_side = q.get(timeout=200)
-        assert not isinstance(best, str), best
-        results[rank] = (best, has_ckpt, has_side)
-    for p in procs:
-        p.join(timeout=60)
+    try:
+        for _ in range(2):
+            rank, best, has_ckpt, has_side = q.get(timeout=200)
+            assert not isinstance(best, str), best
+            results[rank] = (best, has_ckpt, has_side)
+        for p in procs:
+            p.join(timeout=60)
+    finally:
+        # a failed rank must not leave its peer waiting in a collective
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+                p.join(timeout=10)
     # identical best-val on both ranks (all-reduced), rank 0 wrote files
     assert results[0][0] == pytest.approx(results[1][0], rel=1e-5)
     assert results[0][1] and results[0][2]

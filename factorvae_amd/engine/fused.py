@@ -121,6 +121,15 @@ class FusedTrainer:
         # kernel (FV_WHH_FUSED=0 restores the standalone TN call)
         self._whh_fused = (self.bf16 and self.H == 64
                            and os.environ.get("FV_WHH_FUSED", "1") != "0")
+        # fp32: shortened backward tail. 1 (default) = paired Whh/Wih
+        # wgrad + LeakyReLU backward in the Wih dgrad's epilogue, results
+        # bit-identical to the old sequence; 2 = also the LayerNorm/W1x
+        # gradients without the dxln GEMM (differs by fp32 rounding);
+        # FV_F32_TAIL=0 restores the old kernel sequence
+        self._f32_tail = 0
+        if not self.bf16:
+            self._f32_tail = {"0": 0, "2": 2}.get(
+                os.environ.get("FV_F32_TAIL", "1"), 1)
         if self.bf16:
             C3 = 3 * self.H
             # padded (+ transposed-padded) weight shadows for the
@@ -373,7 +382,8 @@ class FusedTrainer:
         w["dscores"] = f(N, M)
         w["dgi"] = f(R, 3 * H)
         w["dgh"] = f(R, 3 * H)
-        w["dxp"] = f(R, C)
+        if not self.bf16 and not self._f32_tail:
+            w["dxp"] = f(R, C)
         max_mn = max(3 * H * max(H, C), C * C, M * H, K * max(H, M))
         w["tn_part"] = f(128 * max_mn)
         w["tn_part2"] = f(128 * max_mn)
@@ -402,9 +412,12 @@ class FusedTrainer:
         # (extractor.hip fv_ln_bwd_params): without the upper clamp,
         # yblocks at very large R exceeds the partial buffer
         rpb = min(8192, max(64, (R + ty - 1) // ty))
-        w["ln_part"] = f(((R + rpb - 1) // rpb + 1) * 2 * C)
         w["dzx"] = f(R, C)
-        w["dxln"] = f(R, C)
+        if self._f32_tail != 2:
+            # FV_F32_TAIL=2 never forms dxln (its LayerNorm gradients
+            # come out of ln_w1x_finish)
+            w["ln_part"] = f(((R + rpb - 1) // rpb + 1) * 2 * C)
+            w["dxln"] = f(R, C)
         if self.bf16:
             fb = lambda *shape: torch.zeros(*shape, device=d,
                                             dtype=torch.bfloat16)
@@ -828,6 +841,48 @@ class FusedTrainer:
             else:
                 ext.gemm_nt_bf16_rs(w["dzx_bf"], self.w1xT_p, None,
                                     w["dxln"], None, None, 1.0, False)
+        elif self._f32_tail:
+            # shortened fp32 tail (docs/KERNELS.md): side 1 holds ONE
+            # paired Whh/Wih wgrad launch + one reduce; main runs the
+            # Wih dgrad with the LeakyReLU backward in its epilogue.
+            # Main is the longer chain: its gemm_nn is enqueued BEFORE
+            # the side-stream pair so that, as gru_bwd's first successor
+            # in the captured graph, it stays on gru_bwd's hardware queue
+            # (the successor that changes queue starts ~10 us late;
+            # profiles/f32_tail.md)
+            fork(1)
+            ext.gemm_nn(w["dgi"].view(R, 3 * H), p("Wih"), None, w["dzx"],
+                        1.0, False, False, lrelu_bwd_of=w["xp"])
+            with _on_side(self, 1):
+                ext.gemm_tn_pair(w["dgh"].view(R, 3 * H),
+                                 w["h_prev"].view(R, H), g("Whh"),
+                                 w["dgi"].view(R, 3 * H), w["xp"], g("Wih"),
+                                 w["tn_part"], w["tn_part2"], chunks, False,
+                                 g("bhh"), g("bih"), w["tn_partb"],
+                                 w["tn_partb2"])
+            if self._f32_tail == 2:
+                # opt-in: W1x/LayerNorm gradients straight from
+                # dzx^T @ xhat (no dxln GEMM, no ln_bwd_params pass);
+                # equal to the default only up to fp32 rounding
+                nz = ext.gemm_tn_xhat(w["dzx"], x2d, w["mean"], w["rstd"],
+                                      w["tn_part3"], w["tn_partb3"])
+                ext.ln_w1x_finish(w["tn_part3"], w["tn_partb3"], nz,
+                                  p("W1x"), p("ln_g"), p("ln_b"), g("W1x"),
+                                  g("b1x"), g("ln_g"), g("ln_b"))
+            else:
+                # the old kernels (bit-identical gradients): the W1x
+                # wgrad follows the pair on side 1 (a third concurrent
+                # branch got serialized BEHIND it on the same hardware
+                # queue: pair last, step 4 % slower), the dxln GEMM and
+                # the LayerNorm parameter gradients stay on main's queue
+                fork(1)
+                ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False,
+                            False)
+                with _on_side(self, 1):
+                    ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"],
+                                chunks, False, g("b1x"), w["tn_partb3"])
+                ext.ln_bwd_params(x2d, w["dxln"], w["mean"], w["rstd"],
+                                  w["ln_part"], g("ln_g"), g("ln_b"), chunks)
         else:
             fork(1)
             with _on_side(self, 1):
@@ -845,10 +900,11 @@ class FusedTrainer:
                 ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"], chunks,
                             False, g("b1x"), w["tn_partb3"])
             ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False, False)
-        fork()
-        with _on_side(self):
-            ext.ln_bwd_params(x2d, w["dxln"], w["mean"], w["rstd"],
-                              w["ln_part"], g("ln_g"), g("ln_b"), chunks)
+        if not self._f32_tail:
+            fork()
+            with _on_side(self):
+                ext.ln_bwd_params(x2d, w["dxln"], w["mean"], w["rstd"],
+                                  w["ln_part"], g("ln_g"), g("ln_b"), chunks)
         # join: main waits for all side-stream wgrad work (+ the early
         # comm slice, so the final slice reduce and adam are ordered)
         join_streams = list(sides)

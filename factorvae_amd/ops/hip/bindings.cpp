@@ -13,7 +13,18 @@ extern "C" {
 hipError_t fv_gemm_nt(const float*, const float*, const float*, float*, int,
                       int, int, float, int, int, hipStream_t);
 hipError_t fv_gemm_nn(const float*, const float*, const float*, float*, int,
-                      int, int, float, int, int, hipStream_t);
+                      int, int, float, int, int, const float*, hipStream_t);
+hipError_t fv_gemm_tn_pair(const float*, const float*, float*, float*, float*,
+                           float*, int, const float*, const float*, float*,
+                           float*, float*, float*, int, int, int, int, int,
+                           hipStream_t);
+int fv_tn_xhat_slices(int);
+hipError_t fv_gemm_tn_xhat(const float*, const float*, const float*,
+                           const float*, float*, float*, int, int, int,
+                           hipStream_t);
+hipError_t fv_ln_w1x_finish(const float*, const float*, const float*,
+                            const float*, const float*, float*, float*,
+                            float*, float*, int, int, hipStream_t);
 hipError_t fv_gemm_tn(const float*, const float*, float*, float*, float*,
                       float*, int, int, int, int, int, hipStream_t);
 hipError_t fv_colsum(const float*, float*, int, int, int, hipStream_t);
@@ -210,14 +221,23 @@ void gemm_nt(torch::Tensor A, torch::Tensor W,
 
 void gemm_nn(torch::Tensor A, torch::Tensor B,
              c10::optional<torch::Tensor> bias, torch::Tensor out,
-             double alpha, bool accumulate, bool act_lrelu) {
+             double alpha, bool accumulate, bool act_lrelu,
+             c10::optional<torch::Tensor> lrelu_bwd_of = c10::nullopt) {
   CK(A); CK(B); CK(out);
   const int R = A.size(0), Ci = A.size(1), Co = B.size(1);
   TORCH_CHECK(B.size(0) == Ci && out.size(0) == R && out.size(1) == Co);
   const float* b = nullptr;
   if (bias.has_value()) { CK(*bias); b = fp(*bias); }
+  // optional epilogue: out *= lrelu'(Y), Y the post-activation (R,Co)
+  const float* yp = nullptr;
+  if (lrelu_bwd_of.has_value()) {
+    CK(*lrelu_bwd_of);
+    TORCH_CHECK(lrelu_bwd_of->dim() == 2 && lrelu_bwd_of->size(0) == R &&
+                lrelu_bwd_of->size(1) == Co);
+    yp = fp(*lrelu_bwd_of);
+  }
   RUN(fv_gemm_nn(fp(A), fp(B), b, fpm(out), R, Ci, Co, (float)alpha,
-                 accumulate, act_lrelu, cur_stream()));
+                 accumulate, act_lrelu, yp, cur_stream()));
 }
 
 // ---------------------------------------------------------------- bf16
@@ -407,6 +427,93 @@ void gemm_tn(torch::Tensor A, torch::Tensor B, torch::Tensor out,
   }
   RUN(fv_gemm_tn(fp(A), fp(B), fpm(out), pp, dbp, dbpp, R, M, N,
                  (int)r_chunks, accumulate, cur_stream()));
+}
+
+// Two weight gradients over a common R and M in one launch (+ one
+// reduce): bit-identical to two gemm_tn calls with the same arguments.
+void gemm_tn_pair(torch::Tensor A0, torch::Tensor B0, torch::Tensor out0,
+                  torch::Tensor A1, torch::Tensor B1, torch::Tensor out1,
+                  c10::optional<torch::Tensor> part0,
+                  c10::optional<torch::Tensor> part1, long r_chunks,
+                  bool accumulate, c10::optional<torch::Tensor> db0,
+                  c10::optional<torch::Tensor> db1,
+                  c10::optional<torch::Tensor> db_part0,
+                  c10::optional<torch::Tensor> db_part1) {
+  CK(A0); CK(B0); CK(out0); CK(A1); CK(B1); CK(out1);
+  const int R = A0.size(0), M = A0.size(1);
+  const int N0 = B0.size(1), N1 = B1.size(1);
+  TORCH_CHECK(A1.size(0) == R && A1.size(1) == M && B0.size(0) == R &&
+              B1.size(0) == R, "pair needs a common R and M");
+  TORCH_CHECK(out0.size(0) == M && out0.size(1) == N0 &&
+              out1.size(0) == M && out1.size(1) == N1);
+  TORCH_CHECK(part0.has_value() == part1.has_value() &&
+              db0.has_value() == db1.has_value() &&
+              db_part0.has_value() == db_part1.has_value(),
+              "pair arguments come in twos");
+  float *pp0 = nullptr, *pp1 = nullptr;
+  if (part0.has_value()) {
+    CK(*part0); CK(*part1);
+    TORCH_CHECK(part0->numel() >= (long)32 * M * N0 &&
+                part1->numel() >= (long)32 * M * N1,
+                "tn partial workspace too small");
+    TORCH_CHECK(part0->data_ptr() != part1->data_ptr(),
+                "pair needs two distinct partial workspaces");
+    pp0 = fpm(*part0); pp1 = fpm(*part1);
+  }
+  float *dbp0 = nullptr, *dbp1 = nullptr, *dbpp0 = nullptr, *dbpp1 = nullptr;
+  if (db0.has_value()) {
+    CK(*db0); CK(*db1);
+    TORCH_CHECK(db0->numel() == M && db1->numel() == M, "db must be (M,)");
+    dbp0 = fpm(*db0); dbp1 = fpm(*db1);
+    if (db_part0.has_value()) {
+      CK(*db_part0); CK(*db_part1);
+      TORCH_CHECK(db_part0->numel() >= (long)32 * M &&
+                  db_part1->numel() >= (long)32 * M,
+                  "db partial workspace too small");
+      TORCH_CHECK(db_part0->data_ptr() != db_part1->data_ptr(),
+                  "pair needs two distinct db partial workspaces");
+      dbpp0 = fpm(*db_part0); dbpp1 = fpm(*db_part1);
+    }
+  }
+  RUN(fv_gemm_tn_pair(fp(A0), fp(B0), fpm(out0), pp0, dbp0, dbpp0, N0,
+                      fp(A1), fp(B1), fpm(out1), pp1, dbp1, dbpp1, N1, R, M,
+                      (int)r_chunks, accumulate, cur_stream()));
+}
+
+// part[z](M,N) = A[slice z]^T @ ((x - mean) * rstd)[slice z],
+// db_part[z](M) = colsum(A[slice z]); returns the slice count z.
+long gemm_tn_xhat(torch::Tensor A, torch::Tensor x, torch::Tensor mean,
+                  torch::Tensor rstd, torch::Tensor part,
+                  torch::Tensor db_part) {
+  CK(A); CK(x); CK(mean); CK(rstd); CK(part); CK(db_part);
+  const int R = A.size(0), M = A.size(1), N = x.size(1);
+  TORCH_CHECK(x.size(0) == R && mean.numel() == R && rstd.numel() == R);
+  const int nz = fv_tn_xhat_slices(R);
+  TORCH_CHECK(part.numel() >= (long)nz * M * N,
+              "tn partial workspace too small");
+  TORCH_CHECK(db_part.numel() >= (long)nz * M,
+              "db partial workspace too small");
+  RUN(fv_gemm_tn_xhat(fp(A), fp(x), fp(mean), fp(rstd), fpm(part),
+                      fpm(db_part), R, M, N, cur_stream()));
+  return nz;
+}
+
+// LayerNorm + W1x parameter gradients from gemm_tn_xhat's slices
+void ln_w1x_finish(torch::Tensor part, torch::Tensor db_part, long nz,
+                   torch::Tensor W1x, torch::Tensor gamma, torch::Tensor beta,
+                   torch::Tensor gW1x, torch::Tensor gb1x,
+                   torch::Tensor dgamma, torch::Tensor dbeta) {
+  CK(part); CK(db_part); CK(W1x); CK(gamma); CK(beta); CK(gW1x); CK(gb1x);
+  CK(dgamma); CK(dbeta);
+  const int C = W1x.size(0);
+  TORCH_CHECK(W1x.dim() == 2 && W1x.size(1) == C && gW1x.numel() == (long)C * C);
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && gb1x.numel() == C &&
+              dgamma.numel() == C && dbeta.numel() == C);
+  TORCH_CHECK(nz >= 1 && nz <= 32 && part.numel() >= nz * (long)C * C &&
+              db_part.numel() >= nz * (long)C, "slice workspace too small");
+  RUN(fv_ln_w1x_finish(fp(part), fp(db_part), fp(W1x), fp(gamma), fp(beta),
+                       fpm(gW1x), fpm(gb1x), fpm(dgamma), fpm(dbeta), C,
+                       (int)nz, cur_stream()));
 }
 
 void colsum(torch::Tensor A, torch::Tensor out, long r_chunks) {
@@ -1014,7 +1121,17 @@ void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_nt", &gemm_nt);
-  mod.def("gemm_nn", &gemm_nn);
+  mod.def("gemm_nn", &gemm_nn, py::arg("A"), py::arg("B"), py::arg("bias"),
+          py::arg("out"), py::arg("alpha"), py::arg("accumulate"),
+          py::arg("act_lrelu"), py::arg("lrelu_bwd_of") = py::none());
+  mod.def("gemm_tn_pair", &gemm_tn_pair, py::arg("A0"), py::arg("B0"),
+          py::arg("out0"), py::arg("A1"), py::arg("B1"), py::arg("out1"),
+          py::arg("part0"), py::arg("part1"), py::arg("r_chunks"),
+          py::arg("accumulate"), py::arg("db0") = py::none(),
+          py::arg("db1") = py::none(), py::arg("db_part0") = py::none(),
+          py::arg("db_part1") = py::none());
+  mod.def("gemm_tn_xhat", &gemm_tn_xhat);
+  mod.def("ln_w1x_finish", &ln_w1x_finish);
   mod.def("gemm_tn", &gemm_tn, py::arg("A"), py::arg("B"), py::arg("out"),
           py::arg("part"), py::arg("r_chunks"), py::arg("accumulate"),
           py::arg("db") = py::none(), py::arg("db_part") = py::none());

@@ -9,6 +9,9 @@
 //   gemm_nn:  out(R,Co)  = act(alpha * (A(R,Ci) @ B(Ci,Co) + bias))    [+=]
 //   gemm_tn:  out(M,N)  (+)= A(R,M)^T @ B(R,N)    (weight grads; R-chunked
 //             slices write partials, reduced in fixed order: deterministic)
+//   gemm_tn_pair: two gemm_tn problems over a common R, M in one launch
+//   gemm_tn_xhat + ln_w1x_finish: W1x/b1x/LayerNorm gradients from
+//             dzx^T @ xhat slices (no dxln; docs/KERNELS.md)
 //   colsum:   out(C)    (+)= sum_r A(R,C)         (bias grads)
 
 #include "common.h"
@@ -20,7 +23,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define BK 32
 
 // act: 0 = none, 1 = leaky_relu(0.01)
-// flags bit0: accumulate into out; bit1: apply act; bit2: bias present
+// flags bit0: accumulate into out; bit1: apply act; bit2: bias present;
+// bit3 (gemm_nn only): multiply by lrelu'(Y) recovered from the
+// post-activation Y(R,Co) — the fused form of gemm_nn -> lrelu_bwd
 // Register double buffer: the next k-tile's global loads issue while
 // the current tile's MFMAs run (f32 MFMA is only 1/16 of bf16 peak, but
 // without the prefetch these mid-size GEMMs were global-latency-bound
@@ -122,8 +127,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
 
 __global__ __launch_bounds__(256) void gemm_nn_kernel(
     const float* __restrict__ A, const float* __restrict__ B,
-    const float* __restrict__ bias, float* __restrict__ out,
-    int R, int Ci, int Co, float alpha, int flags) {
+    const float* __restrict__ bias, const float* __restrict__ Y,
+    float* __restrict__ out, int R, int Ci, int Co, float alpha, int flags) {
   __shared__ float As[2][BR][BK + 1];
   __shared__ float Bs[2][BK][BC + 1];
 
@@ -208,6 +213,7 @@ __global__ __launch_bounds__(256) void gemm_nn_kernel(
       if (flags & 4) v += bias[gc];
       v *= alpha;
       if (flags & 2) v = lrelu_(v);
+      if (flags & 8) v *= lrelu_grad_from_out_(Y[(long)gr * Co + gc]);
       float* o = &out[(long)gr * Co + gc];
       if (flags & 1) v += *o;
       *o = v;
@@ -226,18 +232,27 @@ __global__ __launch_bounds__(256) void gemm_nn_kernel(
 #define TM 32
 #define TN_ 32
 #define TKR 32
-__global__ __launch_bounds__(256) void gemm_tn_kernel(
+//
+// The body is shared by three entry points: gemm_tn_kernel (tile = block
+// x/y), gemm_tn_pair_kernel (two problems with a common R and M, tile
+// index flattened over both) and gemm_tn_xhat_kernel (XHAT: the B
+// operand is staged as LayerNorm's xhat = (x - mean[r]) * rstd[r],
+// ln_fwd's expression, computed while loading x; always per-slice
+// partials). (bx, by, bz) is the tile/slice, nz the slice count.
+template <bool XHAT>
+__device__ __forceinline__ void gemm_tn_body(
     const float* __restrict__ A, const float* __restrict__ B,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
     float* __restrict__ out, float* __restrict__ part,
     float* __restrict__ db, float* __restrict__ db_part,
-    int R, int M, int N, int accumulate) {
+    int R, int M, int N, int accumulate, int bx, int by, int bz, int nz) {
   __shared__ float As[2][TKR][TM + 1];
   __shared__ float Bs[2][TKR][TN_ + 1];
 
-  const int m0 = blockIdx.x * TM;
-  const int n0 = blockIdx.y * TN_;
-  const int chunk = (R + gridDim.z - 1) / gridDim.z;
-  const int rbeg = blockIdx.z * chunk;
+  const int m0 = bx * TM;
+  const int n0 = by * TN_;
+  const int chunk = (R + nz - 1) / nz;
+  const int rbeg = bz * chunk;
   const int rend = min(rbeg + chunk, R);
 
   const int tid = threadIdx.x;
@@ -248,9 +263,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
   const int mt = (wv & 1) * 16;   // m-tile offset
   const int nt = (wv >> 1) * 16;  // n-tile offset
 
-  const bool do_bias = (db != nullptr) && (blockIdx.y == 0);
-  const int bcol = tid & 31;       // bias: thread -> column m0+bcol
-  const int bgrp = tid >> 5;       // 8 row-groups
+  const bool do_bias = (db != nullptr || (XHAT && db_part != nullptr)) &&
+                       (by == 0);
   float bsum = 0.0f;
 
   f32x4 acc = {0, 0, 0, 0};
@@ -260,20 +274,30 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
   const int s_kr0 = tid >> 5;
   const int s_c = tid & 31;
   const int ktiles = (rend - rbeg + TKR - 1) / TKR;
-  float pa[4], pb[4];
+  float pa[4], pb[4], pmu[4], prs[4];
   auto stage_regs = [&](int r0_) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int gr = r0_ + s_kr0 + 8 * u;
       pa[u] = (gr < rend && m0 + s_c < M) ? A[(long)gr * M + m0 + s_c] : 0.0f;
-      pb[u] = (gr < rend && n0 + s_c < N) ? B[(long)gr * N + n0 + s_c] : 0.0f;
+      pb[u] = (gr < rend && n0 + s_c < N) ? B[(long)gr * N + n0 + s_c]
+                                          : 0.0f;
+      if (XHAT) {
+        // raw x, mean, rstd stay in registers; xhat is formed at the LDS
+        // store so the loads keep flying under the MFMAs (rstd = 0 makes
+        // out-of-range rows/columns contribute exactly 0)
+        const bool ok = gr < rend && n0 + s_c < N;
+        pmu[u] = ok ? mean[gr] : 0.0f;
+        prs[u] = ok ? rstd[gr] : 0.0f;
+      }
     }
   };
   auto regs_to_lds = [&](int buf) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       As[buf][s_kr0 + 8 * u][s_c] = pa[u];
-      Bs[buf][s_kr0 + 8 * u][s_c] = pb[u];
+      Bs[buf][s_kr0 + 8 * u][s_c] =
+          XHAT ? (pb[u] - pmu[u]) * prs[u] : pb[u];
     }
   };
   auto bias_from_regs = [&]() {
@@ -306,7 +330,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
     }
   }
 
-  const bool direct = (gridDim.z == 1);
+  const bool direct = !XHAT && (nz == 1);
   if (do_bias) {
     // LDS-reduce the 8 row-group partials per column (reuse As storage)
     __syncthreads();
@@ -321,7 +345,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
         if (direct) {
           if (accumulate) db[gm] += s; else db[gm] = s;
         } else {
-          db_part[(long)blockIdx.z * M + gm] = s;
+          db_part[(long)bz * M + gm] = s;
         }
       }
     }
@@ -330,7 +354,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
   const int gn = n0 + nt + fi;
   if (gn >= N) return;
   float* dst;
-  float* po = direct ? out : part + (long)blockIdx.z * M * N;
+  float* po = direct ? out : part + (long)bz * M * N;
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int gm = m0 + mt + (lane >> 4) * 4 + rr;
@@ -343,20 +367,69 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(
   }
 }
 
+__global__ __launch_bounds__(256) void gemm_tn_kernel(
+    const float* __restrict__ A, const float* __restrict__ B,
+    float* __restrict__ out, float* __restrict__ part,
+    float* __restrict__ db, float* __restrict__ db_part,
+    int R, int M, int N, int accumulate) {
+  gemm_tn_body<false>(A, B, nullptr, nullptr, out, part, db, db_part, R, M, N,
+                      accumulate, blockIdx.x, blockIdx.y, blockIdx.z,
+                      gridDim.z);
+}
+
+// Two TN problems with a common R and M in one launch (the GRU's Whh and
+// Wih weight gradients): blockIdx.x enumerates problem 0's
+// (m-tile, n-tile) pairs, then problem 1's. Each tile runs the shared
+// body, so every element sees the summation order of a separate
+// gemm_tn call.
+struct TnProblem {
+  const float* A;
+  const float* B;
+  float* out;
+  float* part;
+  float* db;
+  float* db_part;
+  int N;
+};
+__global__ __launch_bounds__(256) void gemm_tn_pair_kernel(
+    TnProblem p0, TnProblem p1, int R, int M, int accumulate) {
+  const int mtiles = (M + TM - 1) / TM;
+  const int tiles0 = mtiles * ((p0.N + TN_ - 1) / TN_);
+  const bool second = (int)blockIdx.x >= tiles0;
+  const int tile = second ? (int)blockIdx.x - tiles0 : (int)blockIdx.x;
+  gemm_tn_body<false>(second ? p1.A : p0.A, second ? p1.B : p0.B, nullptr,
+                      nullptr, second ? p1.out : p0.out,
+                      second ? p1.part : p0.part, second ? p1.db : p0.db,
+                      second ? p1.db_part : p0.db_part, R, M,
+                      second ? p1.N : p0.N, accumulate, tile % mtiles,
+                      tile / mtiles, blockIdx.z, gridDim.z);
+}
+
+// part[z](M,N) = A[slice z]^T @ xhat[slice z], db_part[z](M) =
+// colsum(A[slice z]) with xhat = (x - mean) * rstd formed while staging x.
+__global__ __launch_bounds__(256) void gemm_tn_xhat_kernel(
+    const float* __restrict__ A, const float* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ part, float* __restrict__ db_part,
+    int R, int M, int N) {
+  gemm_tn_body<true>(A, x, mean, rstd, nullptr, part, nullptr, db_part, R, M,
+                     N, 0, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
+}
+
 // out[e] += sum_z part[z][e]; db[m] += sum_z db_part[z][m] — fixed z
 // order (deterministic reduce, no atomics).
 // 64 output elements per workgroup; the 4 waves each sum a fixed
 // quarter of the z slices (coalesced across elements) and combine
 // through LDS in fixed order - deterministic, 4x the wave parallelism
 // of a thread-per-element loop (see tn_reduce_bf16_kernel).
-__global__ __launch_bounds__(256) void tn_reduce_kernel(
+__device__ __forceinline__ void tn_reduce_body(
     const float* __restrict__ part, float* __restrict__ out, long elems,
     const float* __restrict__ db_part, float* __restrict__ db, long m_elems,
-    int z, int accumulate) {
+    int z, int accumulate, long block) {
   __shared__ float ps[4][64];
   const int el = threadIdx.x & 63;
   const int zg = threadIdx.x >> 6;
-  const long e = (long)blockIdx.x * 64 + el;
+  const long e = block * 64 + el;
   const int zchunk = (z + 3) / 4;
   const int zbeg = zg * zchunk;
   const int zend = min(zbeg + zchunk, z);
@@ -377,6 +450,103 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(
       const long m = e - elems;
       db[m] = (accumulate ? db[m] : 0.0f) + t;
     }
+  }
+}
+
+__global__ __launch_bounds__(256) void tn_reduce_kernel(
+    const float* __restrict__ part, float* __restrict__ out, long elems,
+    const float* __restrict__ db_part, float* __restrict__ db, long m_elems,
+    int z, int accumulate) {
+  tn_reduce_body(part, out, elems, db_part, db, m_elems, z, accumulate,
+                 blockIdx.x);
+}
+
+// the reduce of gemm_tn_pair_kernel: problem 0's blocks, then problem 1's
+__global__ __launch_bounds__(256) void tn_reduce_pair_kernel(
+    TnProblem p0, TnProblem p1, int M, int has_db, int z, int accumulate) {
+  const long m_elems = has_db ? M : 0;
+  const long e0 = (long)M * p0.N;
+  const int blocks0 = (int)((e0 + m_elems + 63) / 64);
+  const bool second = (int)blockIdx.x >= blocks0;
+  tn_reduce_body(second ? p1.part : p0.part, second ? p1.out : p0.out,
+                 (long)M * (second ? p1.N : p0.N),
+                 second ? p1.db_part : p0.db_part, second ? p1.db : p0.db,
+                 m_elems, z, accumulate,
+                 second ? (int)blockIdx.x - blocks0 : (int)blockIdx.x);
+}
+
+// Finish of the dxln-free LayerNorm + W1x backward. With
+// G = dzx^T @ xhat (slices part[z](C,C)) and gb = colsum(dzx) (slices
+// db_part[z](C)), both from gemm_tn_xhat_kernel:
+//   g(b1x)[j]   = gb[j]
+//   g(W1x)[j,c] = gamma[c] * G[j,c] + beta[c] * gb[j]
+//   g(ln_b)[c]  = sum_j gb[j] * W1x[j,c]
+//   g(ln_g)[c]  = sum_j W1x[j,c] * G[j,c]
+// One workgroup per 8 columns c; thread (jl = tid/8, tid%8) walks
+// rows j = jl, jl+128, ... summing the z slices in fixed order, then the
+// 128 row-lane partials of each column combine in a fixed halving tree
+// through LDS: deterministic, no atomics.
+#define LWF_COLS 8
+#define LWF_ROWL 128
+__global__ __launch_bounds__(1024) void ln_w1x_finish_kernel(
+    const float* __restrict__ part, const float* __restrict__ db_part,
+    const float* __restrict__ W, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ gW,
+    float* __restrict__ gb1, float* __restrict__ dgamma,
+    float* __restrict__ dbeta, int C, int nz) {
+  __shared__ float sg[LWF_ROWL][LWF_COLS + 1];
+  __shared__ float sb[LWF_ROWL][LWF_COLS + 1];
+  const int cl = threadIdx.x & (LWF_COLS - 1);
+  const int jl = threadIdx.x / LWF_COLS;
+  const int c = blockIdx.x * LWF_COLS + cl;
+  const bool live = c < C;
+  const float gm = live ? gamma[c] : 0.0f;
+  const float bt = live ? beta[c] : 0.0f;
+  const long cc = (long)C * C;
+  float ag = 0.0f, ab = 0.0f;
+  for (int j = jl; j < C; j += LWF_ROWL) {
+    // slices in groups of 8: the group's 16 loads issue together
+    // (branch-free: indices clamped into range, the adds guarded), the
+    // sums still run in ascending z
+    const float* pj = part + (long)j * C + min(c, C - 1);
+    float G = 0.0f, gbj = 0.0f;
+    for (int z0 = 0; z0 < nz; z0 += 8) {
+      float pv[8], pd[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int z = min(z0 + u, nz - 1);
+        pv[u] = pj[z * cc];
+        pd[u] = db_part[(long)z * C + j];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (z0 + u < nz) {
+          G += pv[u];
+          gbj += pd[u];
+        }
+      }
+    }
+    if (live) {
+      const float w = W[(long)j * C + c];
+      gW[(long)j * C + c] = fmaf(gm, G, bt * gbj);
+      ag = fmaf(w, G, ag);
+      ab = fmaf(gbj, w, ab);
+    }
+    if (blockIdx.x == 0 && cl == 0) gb1[j] = gbj;
+  }
+  sg[jl][cl] = ag;
+  sb[jl][cl] = ab;
+  __syncthreads();
+  for (int h = LWF_ROWL / 2; h > 0; h >>= 1) {
+    if (jl < h) {
+      sg[jl][cl] += sg[jl + h][cl];
+      sb[jl][cl] += sb[jl + h][cl];
+    }
+    __syncthreads();
+  }
+  if (jl == 0 && live) {
+    dgamma[c] = sg[0][cl];
+    dbeta[c] = sb[0][cl];
   }
 }
 
@@ -428,11 +598,13 @@ hipError_t fv_gemm_nt(const float* A, const float* W, const float* bias,
 
 hipError_t fv_gemm_nn(const float* A, const float* B, const float* bias,
                       float* out, int R, int Ci, int Co, float alpha,
-                      int accumulate, int act_lrelu, hipStream_t stream) {
-  int flags = (accumulate ? 1 : 0) | (act_lrelu ? 2 : 0) | (bias ? 4 : 0);
+                      int accumulate, int act_lrelu, const float* lrelu_bwd_of,
+                      hipStream_t stream) {
+  int flags = (accumulate ? 1 : 0) | (act_lrelu ? 2 : 0) | (bias ? 4 : 0) |
+              (lrelu_bwd_of ? 8 : 0);
   dim3 grid((Co + BC - 1) / BC, (R + BR - 1) / BR);
   hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream,
-                     A, B, bias, out, R, Ci, Co, alpha, flags);
+                     A, B, bias, lrelu_bwd_of, out, R, Ci, Co, alpha, flags);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -464,6 +636,77 @@ hipError_t fv_gemm_tn(const float* A, const float* B, float* out,
                        accumulate);
     HIP_CHECK_LAST();
   }
+  return hipSuccess;
+}
+
+// Whh/Wih-style pair: out0(M,N0) = A0^T @ B0, out1(M,N1) = A1^T @ B1 over
+// a common R, bias grads db0/db1(M) optional (both or neither). Same
+// slice rule and per-element summation order as two fv_gemm_tn calls;
+// one GEMM launch + (when sliced) one reduce launch.
+hipError_t fv_gemm_tn_pair(const float* A0, const float* B0, float* out0,
+                           float* part0, float* db0, float* db_part0, int N0,
+                           const float* A1, const float* B1, float* out1,
+                           float* part1, float* db1, float* db_part1, int N1,
+                           int R, int M, int r_chunks, int accumulate,
+                           hipStream_t stream) {
+  if (r_chunks < 1) r_chunks = 1;
+  if (!part0 || !part1) r_chunks = 1;
+  if (r_chunks > 1) {
+    r_chunks = (R + 511) / 512;
+    if (r_chunks > 32) r_chunks = 32;
+    if (r_chunks < 1) r_chunks = 1;
+  }
+  if (r_chunks > 1 && db0 && !(db_part0 && db_part1)) r_chunks = 1;
+  const TnProblem p0 = {A0, B0, out0, part0, db0, db_part0, N0};
+  const TnProblem p1 = {A1, B1, out1, part1, db1, db_part1, N1};
+  const int mtiles = (M + TM - 1) / TM;
+  const int tiles = mtiles * ((N0 + TN_ - 1) / TN_ + (N1 + TN_ - 1) / TN_);
+  hipLaunchKernelGGL(gemm_tn_pair_kernel, dim3(tiles, 1, r_chunks), dim3(256),
+                     0, stream, p0, p1, R, M, accumulate);
+  HIP_CHECK_LAST();
+  if (r_chunks > 1) {
+    const long m_elems = db0 ? M : 0;
+    const long b0 = ((long)M * N0 + m_elems + 63) / 64;
+    const long b1 = ((long)M * N1 + m_elems + 63) / 64;
+    hipLaunchKernelGGL(tn_reduce_pair_kernel, dim3((unsigned)(b0 + b1)),
+                       dim3(256), 0, stream, p0, p1, M, db0 ? 1 : 0, r_chunks,
+                       accumulate);
+    HIP_CHECK_LAST();
+  }
+  return hipSuccess;
+}
+
+// number of R slices fv_gemm_tn_xhat writes (the fv_gemm_tn rule:
+// >= 512 rows per slice, <= 32 slices)
+int fv_tn_xhat_slices(int R) {
+  int z = (R + 511) / 512;
+  if (z > 32) z = 32;
+  if (z < 1) z = 1;
+  return z;
+}
+
+// part[z](M,N) = A(R,M)[slice z]^T @ xhat(R,N)[slice z], db_part[z](M) =
+// colsum(A[slice z]); never reduced here (ln_w1x_finish sums the slices).
+hipError_t fv_gemm_tn_xhat(const float* A, const float* x, const float* mean,
+                           const float* rstd, float* part, float* db_part,
+                           int R, int M, int N, hipStream_t stream) {
+  dim3 grid((M + TM - 1) / TM, (N + TN_ - 1) / TN_, fv_tn_xhat_slices(R));
+  hipLaunchKernelGGL(gemm_tn_xhat_kernel, grid, dim3(256), 0, stream,
+                     A, x, mean, rstd, part, db_part, R, M, N);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_ln_w1x_finish(const float* part, const float* db_part,
+                            const float* W1x, const float* gamma,
+                            const float* beta, float* gW1x, float* gb1x,
+                            float* dgamma, float* dbeta, int C, int nz,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(ln_w1x_finish_kernel,
+                     dim3((C + LWF_COLS - 1) / LWF_COLS), dim3(1024), 0,
+                     stream, part, db_part, W1x, gamma, beta, gW1x, gb1x,
+                     dgamma, dbeta, C, nz);
+  HIP_CHECK_LAST();
   return hipSuccess;
 }
 

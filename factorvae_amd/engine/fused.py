@@ -130,6 +130,10 @@ class FusedTrainer:
         if not self.bf16:
             self._f32_tail = {"0": 0, "2": 2}.get(
                 os.environ.get("FV_F32_TAIL", "1"), 1)
+        # fp32: LayerNorm + W1x projection + GRU input projection as one
+        # kernel (bit-identical); FV_F32_HEAD=0 restores the three launches
+        self._f32_head = (not self.bf16
+                          and os.environ.get("FV_F32_HEAD", "1") != "0")
         if self.bf16:
             C3 = 3 * self.H
             # padded (+ transposed-padded) weight shadows for the
@@ -559,10 +563,20 @@ class FusedTrainer:
             ext.gemm_nt_bf16_rs(w["xp_bf"], self.wih_p, p("bih"), w["gi"],
                                 None, None, 1.0, False)
         else:
-            ext.ln_fwd(x2d, p("ln_g"), p("ln_b"), w["xln"],
-                       w["mean"], w["rstd"], 1e-5)
-            ext.gemm_nt(w["xln"], p("W1x"), p("b1x"), w["xp"], 1.0, False, True)
-            ext.gemm_nt(w["xp"], p("Wih"), p("bih"), w["gi"], 1.0, False, False)
+            # one launch for LayerNorm + both projections; FV_F32_TAIL=2
+            # never reads xln (its tail uses x, mean, rstd), so that R x C
+            # store is skipped. An unsupported shape launches nothing and
+            # returns False: the three kernels below run instead.
+            if not (self._f32_head and ext.extractor_head_fwd(
+                    x2d, p("ln_g"), p("ln_b"), p("W1x"), p("b1x"), p("Wih"),
+                    p("bih"), None if self._f32_tail == 2 else w["xln"],
+                    w["mean"], w["rstd"], w["xp"], w["gi"], 1e-5)):
+                ext.ln_fwd(x2d, p("ln_g"), p("ln_b"), w["xln"],
+                           w["mean"], w["rstd"], 1e-5)
+                ext.gemm_nt(w["xln"], p("W1x"), p("b1x"), w["xp"], 1.0, False,
+                            True)
+                ext.gemm_nt(w["xp"], p("Wih"), p("bih"), w["gi"], 1.0, False,
+                            False)
         if self.bf16 and H == 64:
             # h_seq is a dead output in the engine (backward consumes
             # h_prev + gates4); skip its (N,T,H) write entirely

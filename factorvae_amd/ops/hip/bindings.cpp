@@ -51,6 +51,11 @@ hipError_t fv_lrelu_bwd(const float*, const float*, float*, long, hipStream_t);
 hipError_t fv_ln_fwd(const float*, const float*, const float*, float*, void*,
                      void*, int, float*, float*, long, int, float,
                      hipStream_t);
+hipError_t fv_extractor_head_fwd(const float*, const float*, const float*,
+                                 const float*, const float*, const float*,
+                                 const float*, float*, float*, float*, float*,
+                                 float*, long, int, int, float, int, int*,
+                                 hipStream_t);
 hipError_t fv_gemm_nt_fp8(const void*, const void*, const float*,
                           const float*, float*, void*, void*, int, int, int,
                           int, int, int, float, int, int, hipStream_t);
@@ -551,6 +556,40 @@ void ln_fwd(torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
   TORCH_CHECK(xo || xb || x8, "ln_fwd needs an output");
   RUN(fv_ln_fwd(fp(x), fp(gamma), fp(beta), xo, xb, x8, f8_ld, fpm(mean),
                 fpm(rstd), R, C, (float)eps, cur_stream()));
+}
+
+// LayerNorm -> lrelu(xln @ W1x^T + b1x) -> xp @ Wih^T + bih in one launch,
+// bit-identical to ln_fwd + two gemm_nt calls. Returns false, launching
+// nothing, when the shape is outside the kernel's limits (extractor.hip).
+bool extractor_head_fwd(torch::Tensor x, torch::Tensor gamma,
+                        torch::Tensor beta, torch::Tensor W1x,
+                        torch::Tensor b1x, torch::Tensor Wih,
+                        torch::Tensor bih, c10::optional<torch::Tensor> xln,
+                        torch::Tensor mean, torch::Tensor rstd,
+                        torch::Tensor xp, torch::Tensor gi, double eps,
+                        int64_t strip) {
+  CK(x); CK(gamma); CK(beta); CK(W1x); CK(b1x); CK(Wih); CK(bih);
+  CK(mean); CK(rstd); CK(xp); CK(gi);
+  const int C = x.size(-1);
+  const long R = x.numel() / C;
+  const int G = Wih.size(0);
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && b1x.numel() == C);
+  TORCH_CHECK(W1x.dim() == 2 && W1x.size(0) == C && W1x.size(1) == C);
+  TORCH_CHECK(Wih.dim() == 2 && Wih.size(1) == C && bih.numel() == G);
+  TORCH_CHECK(mean.numel() == R && rstd.numel() == R);
+  TORCH_CHECK(xp.numel() == R * C && gi.numel() == R * (long)G);
+  float* xo = nullptr;
+  if (xln.has_value()) {
+    CK(*xln);
+    TORCH_CHECK(xln->numel() == R * C);
+    xo = fpm(*xln);
+  }
+  int ran = 0;
+  RUN(fv_extractor_head_fwd(fp(x), fp(gamma), fp(beta), fp(W1x), fp(b1x),
+                            fp(Wih), fp(bih), xo, fpm(mean), fpm(rstd),
+                            fpm(xp), fpm(gi), R, C, G, (float)eps, (int)strip,
+                            &ran, cur_stream()));
+  return ran != 0;
 }
 
 inline void check_fp8(const torch::Tensor& t, const char* name) {
@@ -1154,6 +1193,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("gamma"), py::arg("beta"),
           py::arg("xln"), py::arg("mean"), py::arg("rstd"), py::arg("eps"),
           py::arg("xln_bf") = py::none(), py::arg("xln_f8") = py::none());
+  mod.def("extractor_head_fwd", &extractor_head_fwd, py::arg("x"),
+          py::arg("gamma"), py::arg("beta"), py::arg("W1x"), py::arg("b1x"),
+          py::arg("Wih"), py::arg("bih"), py::arg("xln"), py::arg("mean"),
+          py::arg("rstd"), py::arg("xp"), py::arg("gi"), py::arg("eps"),
+          py::arg("strip") = 0);
   mod.def("gemm_nt_fp8", &gemm_nt_fp8, py::arg("A"), py::arg("W"),
           py::arg("bias"), py::arg("inv_sw"), py::arg("out_f32"),
           py::arg("out_bf16"), py::arg("out_fp8"), py::arg("R"),

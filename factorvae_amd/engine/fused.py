@@ -134,6 +134,10 @@ class FusedTrainer:
         # kernel (bit-identical); FV_F32_HEAD=0 restores the three launches
         self._f32_head = (not self.bf16
                           and os.environ.get("FV_F32_HEAD", "1") != "0")
+        # every dtype: the latency-oriented attn_fused_fwd / attn_fused_bwd /
+        # enc_fused_fwd kernels (bit-identical); FV_MID=0 restores the
+        # original kernels
+        self._mid = 0 if os.environ.get("FV_MID", "1") == "0" else 1
         if self.bf16:
             C3 = 3 * self.H
             # padded (+ transposed-padded) weight shadows for the
@@ -613,7 +617,7 @@ class FusedTrainer:
                                    w["a_att"], w["sd"], w["guard"], w["u"],
                                    w["ctx"], w["hm2"], w["pmu"],
                                    w["psig_pre"], w["psig"], w["psig_c"],
-                                   alpha, keep_inv)
+                                   alpha, keep_inv, self._mid)
             else:
                 ext.gemm_nt(w["h"], w["qk"], w["cb"], w["s_att"], alpha,
                             False, False)
@@ -634,7 +638,8 @@ class FusedTrainer:
                               w["scores_enc"], w["a_enc"], w["yp"],
                               p("Wmu_e"), p("bmu_e"), p("Wsig_e"),
                               p("bsig_e"), w["fmu"], w["fsig_pre"],
-                              w["fsig"], w["fsig_c"], w["enc_done"])
+                              w["fsig"], w["fsig_c"], w["enc_done"],
+                              self._mid)
         else:
             ext.gemm_nt(w["h"], p("Wenc"), p("benc"), w["scores_enc"], 1.0,
                         False, False)
@@ -707,7 +712,7 @@ class FusedTrainer:
                                    w["dz2"], w["du"], w["ds"], w["dc"], gWv,
                                    gbv, gq, gWk, gbk, w["hpart"], g("wmu_p"),
                                    g("bmu_p"), g("wsig_p"), g("bsig_p"),
-                                   alpha, keep_inv)
+                                   alpha, keep_inv, self._mid)
             else:
                 ext.pred_mlp_bwd(w["dpmu"], w["dpsig_c"], w["psig"],
                                  w["psig_pre"], w["hm2"], p("wmu_p"),

@@ -96,7 +96,7 @@ hipError_t fv_enc_fused_fwd(const float*, const float*, const float*,
                             const float*, float*, float*, float*,
                             const float*, const float*, const float*,
                             const float*, float*, float*, float*, float*,
-                            int*, int, int, int, int, hipStream_t);
+                            int*, int, int, int, int, int, hipStream_t);
 hipError_t fv_enc_bwd_fused(const float*, const float*, const float*,
                             const float*, const float*, const float*,
                             const float*, const float*, const float*,
@@ -122,14 +122,14 @@ hipError_t fv_attn_fused_bwd(const float*, const float*, const float*,
                              float*, float*, float*, float*, float*, float*,
                              float*, float*, float*, float*, float*, float*,
                              float*, float*, int, int, int, float, float,
-                             hipStream_t);
+                             int, hipStream_t);
 hipError_t fv_attn_fused_fwd(const float*, const float*, const float*,
                              const float*, const float*, const float*,
                              const float*, const float*, const float*,
                              const float*, const float*, const float*,
                              float*, float*, int*, float*, float*, float*,
                              float*, float*, float*, float*, int, int, int,
-                             float, float, hipStream_t);
+                             float, float, int, hipStream_t);
 hipError_t fv_attn_softmax_fwd(const float*, const float*, float*, float*,
                                int*, int, int, float, hipStream_t);
 hipError_t fv_attn_ctx_fwd(const float*, const float*, const float*,
@@ -835,7 +835,8 @@ void attn_fused_fwd(torch::Tensor h, torch::Tensor qk, torch::Tensor cb,
                     torch::Tensor guard, torch::Tensor u, torch::Tensor ctx,
                     torch::Tensor hm2, torch::Tensor pmu,
                     torch::Tensor psig_pre, torch::Tensor psig,
-                    torch::Tensor psig_c, double alpha, double keep_inv) {
+                    torch::Tensor psig_c, double alpha, double keep_inv,
+                    int variant) {
   CK(h); CK(qk); CK(cb); CK(Wv); CK(bv); CK(Wl); CK(bl); CK(wmu); CK(bmu);
   CK(wsig); CK(bsig); CK(a); CK(sd); CK(u); CK(ctx); CK(hm2); CK(pmu);
   CK(psig_pre); CK(psig); CK(psig_c);
@@ -848,7 +849,7 @@ void attn_fused_fwd(torch::Tensor h, torch::Tensor qk, torch::Tensor cb,
                         fpm(a), fpm(sd), guard.data_ptr<int>(), fpm(u),
                         fpm(ctx), fpm(hm2), fpm(pmu), fpm(psig_pre),
                         fpm(psig), fpm(psig_c), N, K, H, (float)alpha,
-                        (float)keep_inv, cur_stream()));
+                        (float)keep_inv, variant, cur_stream()));
 }
 
 void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
@@ -864,7 +865,7 @@ void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
                     torch::Tensor hpart,
                     torch::Tensor dwmu, torch::Tensor dbmu,
                     torch::Tensor dwsig, torch::Tensor dbsig,
-                    double alpha, double keep_inv) {
+                    double alpha, double keep_inv, int variant) {
   CK(h); CK(a); CK(sd); CK(u); CK(Wv); CK(q); CK(Wk); CK(bk); CK(dz2);
   CK(du); CK(ds); CK(dc); CK(dWv); CK(dbv); CK(dq); CK(dWk); CK(dbk);
   CK(hpart);
@@ -879,7 +880,7 @@ void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
                         fpm(dc), fpm(dWv), fpm(dbv), fpm(dq), fpm(dWk),
                         fpm(dbk), fpm(hpart), fpm(dwmu), fpm(dbmu),
                         fpm(dwsig), fpm(dbsig), N, K, H, (float)alpha,
-                        (float)keep_inv, cur_stream()));
+                        (float)keep_inv, variant, cur_stream()));
 }
 
 void enc_fused_fwd(torch::Tensor h, torch::Tensor Wenc, torch::Tensor benc,
@@ -893,7 +894,8 @@ void enc_fused_fwd(torch::Tensor h, torch::Tensor Wenc, torch::Tensor benc,
                    c10::optional<torch::Tensor> fsig_pre = c10::nullopt,
                    c10::optional<torch::Tensor> fsig = c10::nullopt,
                    c10::optional<torch::Tensor> fsig_c = c10::nullopt,
-                   c10::optional<torch::Tensor> done = c10::nullopt) {
+                   c10::optional<torch::Tensor> done = c10::nullopt,
+                   int variant = 1) {
   CK(h); CK(Wenc); CK(benc); CK(y); CK(scores); CK(a); CK(yp);
   const int N = h.size(0), H = h.size(1), M = Wenc.size(0);
   const float* wm = nullptr; const float* bm = nullptr;
@@ -915,7 +917,7 @@ void enc_fused_fwd(torch::Tensor h, torch::Tensor Wenc, torch::Tensor benc,
   }
   RUN(fv_enc_fused_fwd(fp(h), fp(Wenc), fp(benc), fp(y), fpm(scores),
                        fpm(a), fpm(yp), wm, bm, ws, bs, fm, fsp, fs, fsc,
-                       dn, K, N, M, H, cur_stream()));
+                       dn, K, N, M, H, variant, cur_stream()));
 }
 
 void enc_bwd_fused(torch::Tensor dfmu, torch::Tensor dfsig_c,
@@ -1208,7 +1210,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ln_bwd_params", &ln_bwd_params);
   mod.def("gru_fwd", &gru_fwd);
   mod.def("gru_fwd_mfma", &gru_fwd_mfma);
-  mod.def("attn_fused_fwd", &attn_fused_fwd);
+  // variant: 1 = latency-oriented kernel (default), 0 = original kernel
+  mod.def("attn_fused_fwd", &attn_fused_fwd,
+          py::arg("h"), py::arg("qk"), py::arg("cb"), py::arg("mask"),
+          py::arg("Wv"), py::arg("bv"), py::arg("Wl"), py::arg("bl"),
+          py::arg("wmu"), py::arg("bmu"), py::arg("wsig"), py::arg("bsig"),
+          py::arg("a"), py::arg("sd"), py::arg("guard"), py::arg("u"),
+          py::arg("ctx"), py::arg("hm2"), py::arg("pmu"), py::arg("psig_pre"),
+          py::arg("psig"), py::arg("psig_c"), py::arg("alpha"),
+          py::arg("keep_inv"),
+          py::arg("variant") = 1);
   mod.def("enc_fused_fwd", &enc_fused_fwd, py::arg("h"),
           py::arg("Wenc"), py::arg("benc"), py::arg("y"),
           py::arg("scores"), py::arg("a"), py::arg("yp"),
@@ -1218,9 +1229,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("fsig_pre") = py::none(),
           py::arg("fsig") = py::none(),
           py::arg("fsig_c") = py::none(),
-          py::arg("done") = py::none());
+          py::arg("done") = py::none(), py::arg("variant") = 1);
   mod.def("enc_bwd_fused", &enc_bwd_fused);
-  mod.def("attn_fused_bwd", &attn_fused_bwd);
+  mod.def("attn_fused_bwd", &attn_fused_bwd,
+          py::arg("dpmu"), py::arg("dpsig_c"), py::arg("psig"),
+          py::arg("psig_pre"), py::arg("hm2"), py::arg("wmu"),
+          py::arg("wsig"), py::arg("Wl"), py::arg("h"), py::arg("a"),
+          py::arg("sd"), py::arg("mask"), py::arg("guard"), py::arg("u"),
+          py::arg("Wv"), py::arg("q"), py::arg("Wk"), py::arg("bk"),
+          py::arg("dz2"), py::arg("du"), py::arg("ds"), py::arg("dc"),
+          py::arg("dWv"), py::arg("dbv"), py::arg("dq"), py::arg("dWk"),
+          py::arg("dbk"), py::arg("hpart"), py::arg("dwmu"), py::arg("dbmu"),
+          py::arg("dwsig"), py::arg("dbsig"), py::arg("alpha"),
+          py::arg("keep_inv"),
+          py::arg("variant") = 1);
   mod.def("gru_bwd_mfma", &gru_bwd_mfma, py::arg("dh_final"),
           py::arg("h_prev"), py::arg("gates4"), py::arg("whh_bf"),
           py::arg("dgi"), py::arg("dgh"), py::arg("N"), py::arg("T"),

@@ -1386,6 +1386,235 @@ class FusedTrainer:
         finally:
             self.training = was_training
 
+    # ------------------------------------------------ batched scoring
+    # default row budget (sum of N_d * T) of one predict_many chunk:
+    # ~2 KB of workspace per row at C=158/H=64, i.e. about 1 GB
+    PREDICT_ROWS = 1 << 19
+
+    def _alloc_infer_ws(self, R: int, Nn: int, D: int, with_beta: bool):
+        """Grow-only inference workspace of predict_many; separate from
+        self.ws / the (N, T) shape cache so scoring never disturbs
+        training buffers or captured graphs."""
+        iw = self.__dict__.setdefault("_iws", {"R": 0, "N": 0, "D": 0})
+        d, C, H, K = self.device, self.C, self.H, self.K
+        f = lambda *shape: torch.empty(*shape, device=d, dtype=torch.float32)
+        if "qk" not in iw:
+            iw["qk"] = f(K, H)
+            iw["cb"] = f(K)
+        if R > iw["R"]:
+            iw["x"] = f(R, C)
+            iw["mean"] = f(R)
+            iw["rstd"] = f(R)
+            iw["gi"] = f(R, 3 * H)
+            iw.pop("xln", None)
+            if self.bf16:
+                # same 8-element tail slack as _alloc_ws: the
+                # register-stationary NT kernel's k-tail fragment may read
+                # a few bytes past the last row
+                fbs = lambda r, c: torch.zeros(
+                    r * c + 8, device=d, dtype=torch.bfloat16)[:r * c].view(r, c)
+                iw["xln_bf"] = fbs(R, C)
+                iw["xp_bf"] = fbs(R, C)
+            else:
+                iw["xp"] = f(R, C)
+            iw["R"] = R
+        if Nn > iw["N"]:
+            iw["h"] = f(Nn, H)
+            iw["eps"] = f(Nn)
+            iw["out"] = f(3, Nn)  # rows: sample, mu, sigma
+            iw.pop("beta", None)
+            iw["N"] = Nn
+        if with_beta and "beta" not in iw:
+            iw["beta"] = f(iw["N"], K)
+        if D > iw["D"]:
+            iw["seg_off"] = torch.empty(D + 1, device=d, dtype=torch.int32)
+            iw["pmu"] = f(D, K)
+            iw["psig_c"] = f(D, K)
+            iw["guard"] = torch.empty(D, K, device=d, dtype=torch.int32)
+            iw["D"] = D
+        return iw
+
+    def _launch_predict_many(self, iw, R: int, Nn: int, D: int, T: int,
+                             max_n: int, with_beta: bool):
+        """Kernel sequence of one packed chunk: extractor head of the
+        engine's dtype over all rows -> GRU without backward state ->
+        segmented prior attention -> segmented decoder."""
+        ext, p = self.ext, self.p
+        C, H = self.C, self.H
+        x2d = iw["x"][:R]
+        mean, rstd, gi = iw["mean"][:R], iw["rstd"][:R], iw["gi"][:R]
+        h = iw["h"][:Nn]
+        if self.bf16:
+            xln_bf = iw["xln_bf"][:R]
+            xp_bf = iw["xp_bf"][:R]
+            ext.ln_fwd(x2d, p("ln_g"), p("ln_b"), None, mean, rstd, 1e-5,
+                       xln_bf)
+            ext.gemm_nt_bf16_rs(xln_bf, self.w1x_p, p("b1x"), None, xp_bf,
+                                None, 1.0, True)
+            ext.gemm_nt_bf16_rs(xp_bf, self.wih_p, p("bih"), gi, None, None,
+                                1.0, False)
+        else:
+            xp = iw["xp"][:R]
+            if not (self._f32_head and ext.extractor_head_fwd(
+                    x2d, p("ln_g"), p("ln_b"), p("W1x"), p("b1x"), p("Wih"),
+                    p("bih"), None, mean, rstd, xp, gi, 1e-5)):
+                if "xln" not in iw:
+                    iw["xln"] = torch.empty(iw["R"], C, device=self.device)
+                xln = iw["xln"][:R]
+                ext.ln_fwd(x2d, p("ln_g"), p("ln_b"), xln, mean, rstd, 1e-5)
+                ext.gemm_nt(xln, p("W1x"), p("b1x"), xp, 1.0, False, True)
+                ext.gemm_nt(xp, p("Wih"), p("bih"), gi, 1.0, False, False)
+        if self.bf16 and H == 64:
+            ext.gru_fwd_mfma_infer(gi, self.whh_bf, p("bhh"), h, Nn, T, H)
+        else:
+            ext.gru_fwd_infer(gi, p("Whh"), p("bhh"), h, Nn, T, H)
+        seg = iw["seg_off"][:D + 1]
+        alpha = 1.0 / math.sqrt(float(H) + 1e-6)
+        ext.attn_seg_fwd(h, seg, max_n, iw["qk"], iw["cb"], self.p_Wv,
+                         self.p_bv, p("Wl"), p("bl"), p("wmu_p"), p("bmu_p"),
+                         p("wsig_p"), p("bsig_p"), iw["pmu"], iw["psig_c"],
+                         iw["guard"], alpha)
+        out = iw["out"]
+        ext.dec_seg_fwd(h, seg, p("W1d"), p("b1d"), p("wmu_d"), p("bmu_d"),
+                        p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"), iw["pmu"],
+                        iw["psig_c"], iw["eps"][:Nn], out[1, :Nn],
+                        out[2, :Nn], out[0, :Nn],
+                        iw["beta"][:Nn] if with_beta else None)
+
+    @torch.no_grad()
+    def predict_many(self, xs, eps=None, return_dist: bool = False,
+                     return_beta: bool = False,
+                     max_rows: Optional[int] = None):
+        """Score many trading days in a few launches.
+
+        xs: list of (N_d, T, C) tensors (N_d may differ; T and C fixed;
+        host or device). eps: optional list of (N_d,) standard-normal
+        draws; when None they are drawn per chunk with torch's generator.
+
+        Returns one entry per day, on the host:
+          score                          (default)
+          (score, mu, sigma)             return_dist
+          (score, beta)                  return_beta
+          (score, mu, sigma, beta)       both
+        score / mu / sigma are (N_d, 1), beta is (N_d, K); score is the
+        reference's stochastic sample mu + eps * sigma, mu and sigma the
+        decoder's predictive mean and risk under the prior.
+
+        Days are packed greedily into chunks whose sum of N_d * T stays
+        within max_rows (default FV_PREDICT_ROWS); a day larger than the
+        budget is its own chunk. Each chunk is one host-to-device copy
+        (host inputs), one kernel sequence over the packed rows and one
+        device-to-host copy. A day's result does not depend on what it is
+        batched with. Uses a dedicated inference workspace: training
+        buffers, the shape/graph cache and the in-graph RNG state are not
+        touched (with eps=None the generator advances, as in predict)."""
+        if self.fp8:
+            raise ValueError("predict_many supports the fp32 and bf16 "
+                             "engines; fp8 scoring is not implemented")
+        if self.K > 128:
+            raise UnsupportedShapeError(
+                f"predict_many supports num_factor <= 128, got {self.K}")
+        xs = list(xs)
+        if eps is not None:
+            eps = list(eps)
+            if len(eps) != len(xs):
+                raise ValueError("eps must hold one (N_d,) tensor per day")
+        if not xs:
+            return []
+        T = xs[0].shape[1]
+        for i, x in enumerate(xs):
+            if x.ndim != 3 or x.shape[1] != T or x.shape[2] != self.C:
+                raise ValueError(
+                    f"day {i}: expected (N, {T}, {self.C}), got "
+                    f"{tuple(x.shape)}")
+            if eps is not None and eps[i].numel() != x.shape[0]:
+                raise ValueError(f"day {i}: eps must have {x.shape[0]} "
+                                 f"entries, got {eps[i].numel()}")
+        if max_rows is None:
+            max_rows = (int(os.environ.get("FV_PREDICT_ROWS", "0"))
+                        or self.PREDICT_ROWS)
+        # greedy chunking
+        chunks, cur, rows = [], [], 0
+        for i, x in enumerate(xs):
+            r = x.shape[0] * T
+            if cur and rows + r > max_rows:
+                chunks.append(cur)
+                cur, rows = [], 0
+            cur.append(i)
+            rows += r
+        chunks.append(cur)
+
+        ext, C = self.ext, self.C
+        # everything below runs on the caller's stream: order it after any
+        # training step still in flight on the priority stream
+        self._main_exit()
+        results = [None] * len(xs)
+        qk_done = False
+        for idxs in chunks:
+            lens = [xs[i].shape[0] for i in idxs]
+            Nn, D = sum(lens), len(idxs)
+            R = Nn * T
+            if Nn == 0:
+                for i in idxs:
+                    results[i] = self._pm_entry(
+                        torch.empty(3, 0), torch.empty(0, self.K), 0, 0,
+                        return_dist, return_beta)
+                continue
+            iw = self._alloc_infer_ws(R, Nn, D, return_beta)
+            if not qk_done:
+                ext.attn_qk_fwd(self.p_q, self.p_Wk, self.p_bk, iw["qk"],
+                                iw["cb"])
+                qk_done = True
+            offs = [0]
+            for n in lens:
+                offs.append(offs[-1] + n)
+            iw["seg_off"][:D + 1].copy_(
+                torch.tensor(offs, dtype=torch.int32), non_blocking=False)
+            xd = iw["x"][:R]
+            flat = [xs[i].reshape(-1, C) for i in idxs]
+            if all(t.device.type == "cpu" for t in flat):
+                host = torch.cat([t.float() for t in flat], dim=0)
+                xd.copy_(host)
+            elif all(t.device == xd.device and t.dtype == xd.dtype
+                     for t in flat):
+                torch.cat(flat, dim=0, out=xd)  # one packing kernel
+            else:
+                for t, o, n in zip(flat, offs, lens):
+                    xd[o * T:(o + n) * T].copy_(t)
+            if eps is None:
+                iw["eps"][:Nn].normal_()
+            else:
+                e_host = [eps[i].reshape(-1).float() for i in idxs]
+                if all(t.device.type == "cpu" for t in e_host):
+                    iw["eps"][:Nn].copy_(torch.cat(e_host))
+                elif all(t.device == xd.device for t in e_host):
+                    torch.cat(e_host, out=iw["eps"][:Nn])
+                else:
+                    for t, o, n in zip(e_host, offs, lens):
+                        iw["eps"][o:o + n].copy_(t)
+            self._launch_predict_many(iw, R, Nn, D, T, max(lens),
+                                      return_beta)
+            out = iw["out"][:, :Nn].cpu()  # the chunk's one D2H copy
+            beta = iw["beta"][:Nn].cpu() if return_beta else None
+            for i, o, n in zip(idxs, offs, lens):
+                results[i] = self._pm_entry(out, beta, o, n, return_dist,
+                                            return_beta)
+        return results
+
+    @staticmethod
+    def _pm_entry(out, beta, o: int, n: int, return_dist: bool,
+                  return_beta: bool):
+        score = out[0, o:o + n].reshape(n, 1)
+        if not (return_dist or return_beta):
+            return score
+        entry = [score]
+        if return_dist:
+            entry += [out[1, o:o + n].reshape(n, 1),
+                      out[2, o:o + n].reshape(n, 1)]
+        if return_beta:
+            entry.append(beta[o:o + n])
+        return tuple(entry)
+
     # ------------------------------------------------------------- epochs
     # steps per multi-step training graph (real-epoch batching)
     TRAIN_GRAPH_STEPS = 8

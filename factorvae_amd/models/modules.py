@@ -133,6 +133,12 @@ class FactorDecoder(nn.Module):
         return mu + eps * sigma
 
     def forward(self, stock_latent, factor_mu, factor_sigma):
+        return self.reparameterize(
+            *self.dist(stock_latent, factor_mu, factor_sigma))
+
+    def dist(self, stock_latent, factor_mu, factor_sigma):
+        """(mu, sigma) of the decoded return distribution — what forward
+        samples from."""
         alpha_mu, alpha_sigma = self.alpha_layer(stock_latent)
         beta = self.beta_layer(stock_latent)
 
@@ -145,7 +151,7 @@ class FactorDecoder(nn.Module):
 
         mu = alpha_mu + torch.matmul(beta, factor_mu)
         sigma = torch.sqrt(alpha_sigma ** 2 + torch.matmul(beta ** 2, factor_sigma ** 2) + 1e-6)
-        return self.reparameterize(mu, sigma)
+        return mu, sigma
 
 
 class AttentionLayer(nn.Module):
@@ -298,6 +304,16 @@ class FactorVAE(nn.Module):
         stock_latent = self.feature_extractor(x)
         pred_mu, pred_sigma = self.factor_predictor(stock_latent)
         return self.factor_decoder(stock_latent, pred_mu, pred_sigma)
+
+    @torch.no_grad()
+    def prediction_dist(self, x: torch.Tensor):
+        """Predictive mean and risk (mu, sigma), each (N, 1), of the
+        distribution prediction(x) draws its sample from:
+        prediction(x) == mu + eps * sigma for the eps it draws. Beyond the
+        reference, which only returns the sample."""
+        stock_latent = self.feature_extractor(x)
+        pred_mu, pred_sigma = self.factor_predictor(stock_latent)
+        return self.factor_decoder.dist(stock_latent, pred_mu, pred_sigma)
 
 
 def build_factorvae(num_latent: int = 158, hidden_size: int = 64,

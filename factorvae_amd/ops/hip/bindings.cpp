@@ -175,6 +175,23 @@ hipError_t fv_loss_fused(const float*, const float*, const float*,
 hipError_t fv_dh_combine(float*, const float*, const float*, const float*,
                          const float*, const float*, const float*, int, int,
                          int, int, hipStream_t);
+// batched multi-day scoring (predict.hip + the GRU inference entries)
+hipError_t fv_gru_fwd_infer(const float*, const float*, const float*, float*,
+                            int, int, int, hipStream_t);
+hipError_t fv_gru_fwd_mfma_infer(const float*, const void*, const float*,
+                                 float*, int, int, int, hipStream_t);
+hipError_t fv_attn_seg_fwd(const float*, const int*, const float*,
+                           const float*, const float*, const float*,
+                           const float*, const float*, const float*,
+                           const float*, const float*, const float*, float*,
+                           float*, int*, int, int, int, int, int, float,
+                           hipStream_t);
+hipError_t fv_dec_seg_fwd(const float*, const int*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, float*, float*, float*, float*, int,
+                          int, int, int, hipStream_t);
 hipError_t fv_step_inc(int*, hipStream_t);
 hipError_t fv_adam(float*, const float*, float*, float*, const int*, long,
                    float, float, float, float, float, float, hipStream_t);
@@ -1068,6 +1085,104 @@ void dec_fwd(torch::Tensor h, torch::Tensor W1, torch::Tensor b1,
                  Wb.size(0), h.size(1), cur_stream()));
 }
 
+// ---- batched multi-day scoring ------------------------------------
+inline void check_i32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
+}
+
+void gru_fwd_infer(torch::Tensor gi, torch::Tensor Whh, torch::Tensor bhh,
+                   torch::Tensor h_final, long N, long T, long H) {
+  CK(gi); CK(Whh); CK(bhh); CK(h_final);
+  TORCH_CHECK(gi.numel() >= N * T * 3 * H && h_final.numel() >= N * H &&
+              Whh.numel() == 3 * H * H && bhh.numel() == 3 * H);
+  RUN(fv_gru_fwd_infer(fp(gi), fp(Whh), fp(bhh), fpm(h_final), (int)N,
+                       (int)T, (int)H, cur_stream()));
+}
+
+void gru_fwd_mfma_infer(torch::Tensor gi, torch::Tensor whh_bf,
+                        torch::Tensor bhh, torch::Tensor h_final, long N,
+                        long T, long H) {
+  CK(gi); CKB(whh_bf); CK(bhh); CK(h_final);
+  TORCH_CHECK(gi.numel() >= N * T * 3 * H && h_final.numel() >= N * H &&
+              whh_bf.numel() == 3 * H * H && bhh.numel() == 3 * H);
+  RUN(fv_gru_fwd_mfma_infer(fp(gi), bfpc(whh_bf), fp(bhh), fpm(h_final),
+                            (int)N, (int)T, (int)H, cur_stream()));
+}
+
+// h (sumN,H) packed days; seg_off int32 (D+1) device row offsets; max_n
+// the longest day (host-side knowledge: sizes the launch's LDS).
+// Outputs pmu / psig_c (D,K) fp32 and guard (D,K) int32.
+void attn_seg_fwd(torch::Tensor h, torch::Tensor seg_off, long max_n,
+                  torch::Tensor qk, torch::Tensor cb, torch::Tensor Wv,
+                  torch::Tensor bv, torch::Tensor Wl, torch::Tensor bl,
+                  torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
+                  torch::Tensor bsig, torch::Tensor pmu, torch::Tensor psig_c,
+                  torch::Tensor guard, double alpha) {
+  CK(h); CK(qk); CK(cb); CK(Wv); CK(bv); CK(Wl); CK(bl); CK(wmu); CK(bmu);
+  CK(wsig); CK(bsig); CK(pmu); CK(psig_c);
+  check_i32(seg_off, "seg_off");
+  check_i32(guard, "guard");
+  TORCH_CHECK(h.dim() == 2 && qk.dim() == 2 && qk.size(1) == h.size(1));
+  const long total = h.size(0), H = h.size(1), K = qk.size(0);
+  const long D = seg_off.numel() - 1;
+  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
+  TORCH_CHECK(H <= 64 && K <= 128, "attn_seg_fwd supports H <= 64, K <= 128");
+  TORCH_CHECK(pmu.numel() >= D * K && psig_c.numel() >= D * K &&
+              guard.numel() >= D * K, "per-day outputs too small");
+  TORCH_CHECK(cb.numel() == K && Wv.numel() == K * H * H &&
+              bv.numel() == K * H && Wl.numel() == H * H && bl.numel() == H &&
+              wmu.numel() == H && wsig.numel() == H);
+  TORCH_CHECK(max_n >= 0 && max_n <= total, "max_n outside the packed rows");
+  RUN(fv_attn_seg_fwd(fp(h), seg_off.data_ptr<int>(), fp(qk), fp(cb), fp(Wv),
+                      fp(bv), fp(Wl), fp(bl), fp(wmu), fp(bmu), fp(wsig),
+                      fp(bsig), fpm(pmu), fpm(psig_c), guard.data_ptr<int>(),
+                      (int)total, (int)D, (int)max_n, (int)K, (int)H,
+                      (float)alpha, cur_stream()));
+}
+
+// fmu / fsig_c are (D,K): each row takes its own day's factor prior.
+// eps/sample and beta are optional; sample = fma(eps, sigma, mu).
+void dec_seg_fwd(torch::Tensor h, torch::Tensor seg_off, torch::Tensor W1,
+                 torch::Tensor b1, torch::Tensor wmu, torch::Tensor bmu,
+                 torch::Tensor wsig, torch::Tensor bsig, torch::Tensor Wb,
+                 torch::Tensor bb, torch::Tensor fmu, torch::Tensor fsig_c,
+                 c10::optional<torch::Tensor> eps, torch::Tensor mu,
+                 torch::Tensor sigma, c10::optional<torch::Tensor> sample,
+                 c10::optional<torch::Tensor> beta) {
+  CK(h); CK(W1); CK(b1); CK(wmu); CK(bmu); CK(wsig); CK(bsig); CK(Wb);
+  CK(bb); CK(fmu); CK(fsig_c); CK(mu); CK(sigma);
+  check_i32(seg_off, "seg_off");
+  TORCH_CHECK(h.dim() == 2 && Wb.dim() == 2 && Wb.size(1) == h.size(1));
+  const long N = h.size(0), H = h.size(1), K = Wb.size(0);
+  const long D = seg_off.numel() - 1;
+  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
+  TORCH_CHECK(H <= 64 && K <= 128, "dec_seg_fwd supports H <= 64, K <= 128");
+  TORCH_CHECK(W1.numel() == H * H && b1.numel() == H && wmu.numel() == H &&
+              wsig.numel() == H && bb.numel() == K);
+  TORCH_CHECK(fmu.numel() >= D * K && fsig_c.numel() >= D * K);
+  TORCH_CHECK(mu.numel() >= N && sigma.numel() >= N);
+  const float* ep = nullptr; float* sp = nullptr; float* bp = nullptr;
+  if (eps.has_value()) {
+    CK(*eps);
+    TORCH_CHECK(sample.has_value(), "eps needs a sample output");
+    CK(*sample);
+    TORCH_CHECK(eps->numel() >= N && sample->numel() >= N);
+    ep = fp(*eps);
+    sp = fpm(*sample);
+  }
+  if (beta.has_value()) {
+    CK(*beta);
+    TORCH_CHECK(beta->numel() >= N * K);
+    bp = fpm(*beta);
+  }
+  RUN(fv_dec_seg_fwd(fp(h), seg_off.data_ptr<int>(), fp(W1), fp(b1), fp(wmu),
+                     fp(bmu), fp(wsig), fp(bsig), fp(Wb), fp(bb), fp(fmu),
+                     fp(fsig_c), ep, fpm(mu), fpm(sigma), sp, bp, (int)N,
+                     (int)D, (int)K, (int)H, cur_stream()));
+}
+
 void dec_bwd(torch::Tensor drecon, torch::Tensor h, torch::Tensor a1,
              torch::Tensor beta, torch::Tensor asig_pre, torch::Tensor sigma,
              torch::Tensor eps, torch::Tensor fmu, torch::Tensor fsig_c,
@@ -1291,6 +1406,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("pred_mlp_bwd", &pred_mlp_bwd);
   mod.def("dec_fwd", &dec_fwd);
   mod.def("dec_bwd", &dec_bwd);
+  // batched multi-day scoring (inference only)
+  mod.def("gru_fwd_infer", &gru_fwd_infer);
+  mod.def("gru_fwd_mfma_infer", &gru_fwd_mfma_infer);
+  mod.def("attn_seg_fwd", &attn_seg_fwd,
+          py::arg("h"), py::arg("seg_off"), py::arg("max_n"), py::arg("qk"),
+          py::arg("cb"), py::arg("Wv"), py::arg("bv"), py::arg("Wl"),
+          py::arg("bl"), py::arg("wmu"), py::arg("bmu"), py::arg("wsig"),
+          py::arg("bsig"), py::arg("pmu"), py::arg("psig_c"),
+          py::arg("guard"), py::arg("alpha"));
+  mod.def("dec_seg_fwd", &dec_seg_fwd,
+          py::arg("h"), py::arg("seg_off"), py::arg("W1"), py::arg("b1"),
+          py::arg("wmu"), py::arg("bmu"), py::arg("wsig"), py::arg("bsig"),
+          py::arg("Wb"), py::arg("bb"), py::arg("fmu"), py::arg("fsig_c"),
+          py::arg("eps"), py::arg("mu"), py::arg("sigma"),
+          py::arg("sample") = py::none(), py::arg("beta") = py::none());
   mod.def("loss_fwd", &loss_fwd);
   mod.def("loss_bwd", &loss_bwd);
   mod.def("step_inc", &step_inc);

@@ -21,6 +21,9 @@
 
 #define GRU_SPW 4  // stocks per workgroup (= waves)
 
+// SAVE=false (inference): the backward state (h_seq, h_prev, gates4) is
+// neither written nor touched; the pointers may be null.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
     const float* __restrict__ gi,     // (N,T,3H)
     const float* __restrict__ Whh,    // (3H,H)
@@ -74,14 +77,16 @@ __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
       const float hp_l = hprev[w * H + lane];
       hn = fmaf(z, hp_l - n, n);  // (1-z)*n + z*hp
 
-      const long ob = ((long)s * T + t) * H + lane;
-      if (h_seq) h_seq[ob] = hn;
-      h_prev_out[ob] = hp_l;
-      const long gb = ((long)s * T + t) * 4 * H + lane;
-      gates4[gb] = r;
-      gates4[gb + H] = z;
-      gates4[gb + 2 * H] = n;
-      gates4[gb + 3 * H] = q;
+      if (SAVE) {
+        const long ob = ((long)s * T + t) * H + lane;
+        if (h_seq) h_seq[ob] = hn;
+        h_prev_out[ob] = hp_l;
+        const long gb = ((long)s * T + t) * 4 * H + lane;
+        gates4[gb] = r;
+        gates4[gb + H] = z;
+        gates4[gb + 2 * H] = n;
+        gates4[gb + 3 * H] = q;
+      }
       if (t == T - 1) h_final[(long)s * H + lane] = hn;
     }
     // hprev[w][*] is private to wave w: in-wave LDS dependency only,
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(256) void gru_bwd_generic_kernel(
 //      groups hit disjoint bank quads (bank = j*4 % 64), conflict-free.
 #define GRU_SPW_F 8
 
+template <bool SAVE>
 __global__ __launch_bounds__(512) void gru_fwd_fast_kernel(
     const float* __restrict__ gi, const float* __restrict__ Whh,
     const float* __restrict__ bhh, float* __restrict__ h_final,
@@ -253,14 +259,16 @@ __global__ __launch_bounds__(512) void gru_fwd_fast_kernel(
       const float hp_l = hprev[w * 64 + lane];
       hn = fmaf(z, hp_l - n, n);
 
-      const long ob = ((long)s * T + t) * H + lane;
-      if (h_seq) h_seq[ob] = hn;
-      h_prev_out[ob] = hp_l;
-      const long gb = ((long)s * T + t) * 4 * H + lane;
-      gates4[gb] = r;
-      gates4[gb + H] = z;
-      gates4[gb + 2 * H] = n;
-      gates4[gb + 3 * H] = q;
+      if (SAVE) {
+        const long ob = ((long)s * T + t) * H + lane;
+        if (h_seq) h_seq[ob] = hn;
+        h_prev_out[ob] = hp_l;
+        const long gb = ((long)s * T + t) * 4 * H + lane;
+        gates4[gb] = r;
+        gates4[gb + H] = z;
+        gates4[gb + 2 * H] = n;
+        gates4[gb + 3 * H] = q;
+      }
       if (t == T - 1) h_final[(long)s * H + lane] = hn;
     }
     gir = nir; giz = niz; gin = nin;
@@ -381,6 +389,8 @@ hipError_t fv_gru_fwd_mfma_f32(const float*, const float*, const float*,
 hipError_t fv_gru_bwd_mfma_f32(const float*, const float*, const float*,
                                const float*, float*, float*, int, int, int,
                                hipStream_t);
+hipError_t fv_gru_fwd_mfma_f32_infer(const float*, const float*, const float*,
+                                     float*, int, int, int, hipStream_t);
 
 hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
                       float* h_final, float* h_seq, float* h_prev,
@@ -392,13 +402,39 @@ hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
   if ((H & 3) == 0) {
     const size_t lds = ((size_t)3 * 64 * H + GRU_SPW_F * 64) * sizeof(float);
     dim3 grid((N + GRU_SPW_F - 1) / GRU_SPW_F);
-    hipLaunchKernelGGL(gru_fwd_fast_kernel, grid, dim3(512), lds, stream,
+    hipLaunchKernelGGL(gru_fwd_fast_kernel<true>, grid, dim3(512), lds, stream,
                        gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H);
   } else {
     const size_t lds = ((size_t)H * 3 * H + GRU_SPW * H) * sizeof(float);
     dim3 grid((N + GRU_SPW - 1) / GRU_SPW);
-    hipLaunchKernelGGL(gru_fwd_generic_kernel, grid, dim3(256), lds, stream,
+    hipLaunchKernelGGL(gru_fwd_generic_kernel<true>, grid, dim3(256), lds, stream,
                        gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H);
+  }
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// Inference forward: same recurrence, same h_final bits, no backward
+// state written (the SAVE=false instantiations).
+hipError_t fv_gru_fwd_infer(const float* gi, const float* Whh,
+                            const float* bhh, float* h_final, int N, int T,
+                            int H, hipStream_t stream) {
+  if (H > 64) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  if (H == 64)
+    return fv_gru_fwd_mfma_f32_infer(gi, Whh, bhh, h_final, N, T, H, stream);
+  if ((H & 3) == 0) {
+    const size_t lds = ((size_t)3 * 64 * H + GRU_SPW_F * 64) * sizeof(float);
+    dim3 grid((N + GRU_SPW_F - 1) / GRU_SPW_F);
+    hipLaunchKernelGGL(gru_fwd_fast_kernel<false>, grid, dim3(512), lds,
+                       stream, gi, Whh, bhh, h_final, nullptr, nullptr,
+                       nullptr, N, T, H);
+  } else {
+    const size_t lds = ((size_t)H * 3 * H + GRU_SPW * H) * sizeof(float);
+    dim3 grid((N + GRU_SPW - 1) / GRU_SPW);
+    hipLaunchKernelGGL(gru_fwd_generic_kernel<false>, grid, dim3(256), lds,
+                       stream, gi, Whh, bhh, h_final, nullptr, nullptr,
+                       nullptr, N, T, H);
   }
   HIP_CHECK_LAST();
   return hipSuccess;

@@ -29,6 +29,9 @@ typedef __attribute__((address_space(3))) s16x4_g* lds_v4p_g;
 #define GM_HB 72      // bf16 h image row stride (16B-aligned frags)
 #define GM_GB 200     // bf16 dgh image row stride
 
+// SAVE=false (inference): no h_seq / h_prev / gates4 stores; the pointers
+// may be null.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void gru_fwd_mfma_kernel(
     const float* __restrict__ gi,      // (N,T,192)
     const void* __restrict__ whh_bf_,  // (192,64) bf16
@@ -132,13 +135,15 @@ __global__ __launch_bounds__(256) void gru_fwd_mfma_kernel(
       }
       // global saves (b128-shaped: ej is a multiple of 4)
       const long tb = (erow + t);
-      if (h_seq) *(f32x4*)&h_seq[tb * 64 + ej] = *(f32x4*)hn;
-      *(f32x4*)&h_prev_out[tb * 64 + ej] = *(f32x4*)hp4;
-      float* g4 = &gates4[tb * 256];
-      *(f32x4*)&g4[ej] = *(f32x4*)gr4;
-      *(f32x4*)&g4[64 + ej] = *(f32x4*)gz4;
-      *(f32x4*)&g4[128 + ej] = *(f32x4*)gn4;
-      *(f32x4*)&g4[192 + ej] = *(f32x4*)gq4;
+      if (SAVE) {
+        if (h_seq) *(f32x4*)&h_seq[tb * 64 + ej] = *(f32x4*)hn;
+        *(f32x4*)&h_prev_out[tb * 64 + ej] = *(f32x4*)hp4;
+        float* g4 = &gates4[tb * 256];
+        *(f32x4*)&g4[ej] = *(f32x4*)gr4;
+        *(f32x4*)&g4[64 + ej] = *(f32x4*)gz4;
+        *(f32x4*)&g4[128 + ej] = *(f32x4*)gn4;
+        *(f32x4*)&g4[192 + ej] = *(f32x4*)gq4;
+      }
       if (t == T - 1) *(f32x4*)&h_final[(long)(s0 + es) * 64 + ej] = *(f32x4*)hn;
     }
     if (t + 1 < T) gi_load(t + 1);
@@ -421,6 +426,7 @@ __global__ __launch_bounds__(256) void gru_bwd_mfma_kernel(
 // registers: 48 floats/lane fwd (3 n-tiles x 16 k-steps), 48 bwd.
 #define GMF_SH 68   // fp32 h image stride (2-way worst-case banks)
 
+template <bool SAVE>
 __global__ __launch_bounds__(256) void gru_fwd_mfma_f32_kernel(
     const float* __restrict__ gi, const float* __restrict__ Whh,
     const float* __restrict__ bhh, float* __restrict__ h_final,
@@ -510,13 +516,15 @@ __global__ __launch_bounds__(256) void gru_fwd_mfma_f32_kernel(
         gr4[u] = r; gz4[u] = z; gn4[u] = n; gq4[u] = q; hp4[u] = hp;
       }
       const long tb = (erow + t);
-      if (h_seq) *(f32x4*)&h_seq[tb * 64 + ej] = *(f32x4*)hn;
-      *(f32x4*)&h_prev_out[tb * 64 + ej] = *(f32x4*)hp4;
-      float* g4 = &gates4[tb * 256];
-      *(f32x4*)&g4[ej] = *(f32x4*)gr4;
-      *(f32x4*)&g4[64 + ej] = *(f32x4*)gz4;
-      *(f32x4*)&g4[128 + ej] = *(f32x4*)gn4;
-      *(f32x4*)&g4[192 + ej] = *(f32x4*)gq4;
+      if (SAVE) {
+        if (h_seq) *(f32x4*)&h_seq[tb * 64 + ej] = *(f32x4*)hn;
+        *(f32x4*)&h_prev_out[tb * 64 + ej] = *(f32x4*)hp4;
+        float* g4 = &gates4[tb * 256];
+        *(f32x4*)&g4[ej] = *(f32x4*)gr4;
+        *(f32x4*)&g4[64 + ej] = *(f32x4*)gz4;
+        *(f32x4*)&g4[128 + ej] = *(f32x4*)gn4;
+        *(f32x4*)&g4[192 + ej] = *(f32x4*)gq4;
+      }
       if (t == T - 1)
         *(f32x4*)&h_final[(long)(s0 + es) * 64 + ej] = *(f32x4*)hn;
     }
@@ -628,7 +636,7 @@ hipError_t fv_gru_fwd_mfma(const float* gi, const void* whh_bf,
                            int H, hipStream_t stream) {
   if (H != 64) return hipErrorInvalidValue;
   dim3 grid((N + GM_S - 1) / GM_S);
-  hipLaunchKernelGGL(gru_fwd_mfma_kernel, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(gru_fwd_mfma_kernel<true>, grid, dim3(256), 0, stream,
                      gi, whh_bf, bhh, h_final, h_seq, h_prev, gates4, N, T);
   HIP_CHECK_LAST();
   return hipSuccess;
@@ -640,8 +648,34 @@ hipError_t fv_gru_fwd_mfma_f32(const float* gi, const float* Whh,
                                int N, int T, int H, hipStream_t stream) {
   if (H != 64) return hipErrorInvalidValue;
   dim3 grid((N + GM_S - 1) / GM_S);
-  hipLaunchKernelGGL(gru_fwd_mfma_f32_kernel, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(gru_fwd_mfma_f32_kernel<true>, grid, dim3(256), 0, stream,
                      gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_fwd_mfma_infer(const float* gi, const void* whh_bf,
+                                 const float* bhh, float* h_final, int N,
+                                 int T, int H, hipStream_t stream) {
+  if (H != 64) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GM_S - 1) / GM_S);
+  hipLaunchKernelGGL(gru_fwd_mfma_kernel<false>, grid, dim3(256), 0, stream,
+                     gi, whh_bf, bhh, h_final, nullptr, nullptr, nullptr, N,
+                     T);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_fwd_mfma_f32_infer(const float* gi, const float* Whh,
+                                     const float* bhh, float* h_final, int N,
+                                     int T, int H, hipStream_t stream) {
+  if (H != 64) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GM_S - 1) / GM_S);
+  hipLaunchKernelGGL(gru_fwd_mfma_f32_kernel<false>, grid, dim3(256), 0,
+                     stream, gi, Whh, bhh, h_final, nullptr, nullptr, nullptr,
+                     N, T);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -46,6 +46,15 @@ def build_argparser() -> argparse.ArgumentParser:
                    choices=["auto", "fused", "eager"],
                    help="auto = fused HIP predict path on GPU, eager "
                         "module path otherwise")
+    p.add_argument("--batch_days", type=int, default=1,
+                   help="score this many consecutive days per call of the "
+                        "batched path (1 = one day at a time)")
+    p.add_argument("--dist", action="store_true",
+                   help="also write the predictive mean and risk as mu and "
+                        "sigma columns")
+    p.add_argument("--risk_aversion", type=float, default=0.0,
+                   help="eta != 0: score = mu - eta * sigma (deterministic; "
+                        "implies --dist)")
     p.add_argument("--backtest", action="store_true",
                    help="run the top-k dropout backtest + risk report")
     p.add_argument("--report", action="store_true",
@@ -73,7 +82,10 @@ def main(argv=None):
     loader = init_data_loader(df, step_len=args.seq_length, shuffle=False,
                               start=args.start, end=args.end)
     scores = generate_prediction_scores(model, loader, loader.dataset,
-                                        targs, engine=args.engine)
+                                        targs, engine=args.engine,
+                                        batch_days=args.batch_days,
+                                        return_dist=args.dist,
+                                        risk_aversion=args.risk_aversion)
 
     os.makedirs(args.out_dir, exist_ok=True)
     # reference artifact name schema (scores/readme.md)

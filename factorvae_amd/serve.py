@@ -18,6 +18,10 @@ Endpoints:
                                  (shape (N, T, C)) -> {"scores": [N floats]}
   POST /score_batch           -> body {"days": [ (N_i, T, C) nested lists ]}
                                  -> {"scores": [ [N_i floats] ... ]}
+  POST /score_many            -> body {"days": [...], "dist": false}: every
+                                 day scored in ONE batched GPU call ->
+                                 {"days": [{"scores": [...]} ...]} (plus
+                                 "mu" / "sigma" per day with dist)
 """
 
 from __future__ import annotations
@@ -81,6 +85,41 @@ class ScoringEngine:
             out = self.model.prediction(x)
         return out.reshape(-1).cpu()
 
+    @torch.no_grad()
+    def score_many(self, xs, dist: bool = False):
+        """List of (N_i, T, C) days -> one dict per day with "scores"
+        (and "mu" / "sigma" with dist), all days in one batched call
+        (FusedTrainer.predict_many) on the fused engine."""
+        days = []
+        for x in xs:
+            if x.ndim != 3 or x.shape[1] != self.seq_length \
+                    or x.shape[2] != self.num_latent:
+                raise ValueError(
+                    f"expected (N, {self.seq_length}, {self.num_latent}), "
+                    f"got {tuple(x.shape)}")
+            days.append(x.to(dtype=torch.float32))
+        if self.trainer is not None:
+            outs = self.trainer.predict_many(days, return_dist=dist)
+        else:
+            outs = []
+            for x in days:
+                x = x.to(self.device)
+                if dist:
+                    mu, sigma = self.model.prediction_dist(x)
+                    outs.append((mu + torch.randn_like(sigma) * sigma, mu,
+                                 sigma))
+                else:
+                    outs.append(self.model.prediction(x))
+        res = []
+        for o in outs:
+            if dist:
+                res.append({"scores": o[0].reshape(-1).tolist(),
+                            "mu": o[1].reshape(-1).tolist(),
+                            "sigma": o[2].reshape(-1).tolist()})
+            else:
+                res.append({"scores": o.reshape(-1).tolist()})
+        return res
+
 
 try:  # module-level request models (FastAPI resolves annotations here)
     from fastapi import Request, Response
@@ -91,8 +130,12 @@ try:  # module-level request models (FastAPI resolves annotations here)
 
     class BatchRequest(BaseModel):
         days: List[List[List[List[float]]]]
+
+    class ManyRequest(BaseModel):
+        days: List[List[List[List[float]]]]
+        dist: bool = False
 except ImportError:  # serving extras absent: ScoringEngine still usable
-    ScoreRequest = BatchRequest = Request = Response = None
+    ScoreRequest = BatchRequest = ManyRequest = Request = Response = None
 
 
 def build_app(engine: ScoringEngine):
@@ -126,6 +169,16 @@ def build_app(engine: ScoringEngine):
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
         return {"scores": outs}
+
+    @app.post("/score_many")
+    def score_many(req: ManyRequest):
+        """All days of the request in one batched GPU call; with dist the
+        predictive mean and risk come back next to the scores."""
+        try:
+            days = [torch.tensor(d, dtype=torch.float32) for d in req.days]
+            return {"days": engine.score_many(days, dist=req.dist)}
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
 
     @app.post("/score_raw")
     async def score_raw(request: Request):

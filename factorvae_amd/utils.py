@@ -88,7 +88,9 @@ def checkpoint_path(save_dir: str, run_name: str, num_factor: int,
 
 @torch.no_grad()
 def generate_prediction_scores(model, test_dataloader, test_dataset, args,
-                               engine: str = "auto"):
+                               engine: str = "auto", batch_days: int = 1,
+                               return_dist: bool = False,
+                               risk_aversion: float = 0.0):
     """Score every test cross-section with model.prediction; returns a
     MultiIndex (datetime, instrument) DataFrame['score'].
 
@@ -98,10 +100,21 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
 
     engine="auto" uses the fused HIP predict path on GPU (extractor ->
     prior predictor -> stochastic decoder, same math incl. the eval-time
-    reparameterized sample); "eager" forces the module path."""
+    reparameterized sample); "eager" forces the module path.
+
+    Beyond the reference (the defaults reproduce its frame exactly):
+    batch_days > 1 scores that many consecutive loader days per call of
+    the batched path (FusedTrainer.predict_many; the eager engine loops);
+    return_dist adds the decoder's predictive mean and risk as `mu` and
+    `sigma` columns; risk_aversion = eta != 0 makes `score` the
+    deterministic risk-adjusted mu - eta * sigma (and implies
+    return_dist)."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.to(device)
     model.eval()
+    batch_days = max(1, int(batch_days))
+    risk_aversion = float(risk_aversion)
+    want_dist = bool(return_dist) or risk_aversion != 0.0
     ls = []
 
     trainer = None
@@ -114,21 +127,58 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
         except Exception:
             trainer = None
 
-    for char_with_label, _ in test_dataloader:
-        if char_with_label.shape[1] != args.seq_length:
-            continue
-        char = char_with_label[:, :, :-1].to(device)
-        if trainer is not None:
-            predictions = trainer.predict(char.float())
-        else:
-            predictions = model.prediction(char.float())
-        ls.append(predictions.detach().cpu())
+    if batch_days == 1 and not want_dist:
+        for char_with_label, _ in test_dataloader:
+            if char_with_label.shape[1] != args.seq_length:
+                continue
+            char = char_with_label[:, :, :-1].to(device)
+            if trainer is not None:
+                predictions = trainer.predict(char.float())
+            else:
+                predictions = model.prediction(char.float())
+            ls.append(predictions.detach().cpu())
+        cols = ["score"]
+    else:
+        def flush(days):
+            if not days:
+                return
+            if trainer is not None:
+                outs = trainer.predict_many(days, return_dist=want_dist)
+            else:
+                outs = []
+                for char in days:
+                    char = char.to(device)
+                    if want_dist:
+                        mu, sigma = model.prediction_dist(char)
+                        score = mu + torch.randn_like(sigma) * sigma
+                        outs.append((score, mu, sigma))
+                    else:
+                        outs.append(model.prediction(char))
+            for o in outs:
+                if want_dist:
+                    score, mu, sigma = (t.detach().cpu() for t in o)
+                    if risk_aversion != 0.0:
+                        score = mu - risk_aversion * sigma
+                    ls.append(torch.cat([score, mu, sigma], dim=1))
+                else:
+                    ls.append(o.detach().cpu())
+
+        pending = []
+        for char_with_label, _ in test_dataloader:
+            if char_with_label.shape[1] != args.seq_length:
+                continue
+            pending.append(char_with_label[:, :, :-1].float())
+            if len(pending) == batch_days:
+                flush(pending)
+                pending = []
+        flush(pending)
+        cols = ["score", "mu", "sigma"] if want_dist else ["score"]
 
     ls = torch.cat(ls, dim=0)
     multi_index = pd.MultiIndex.from_tuples(
         test_dataset.get_index(), names=["datetime", "instrument"]
     )
-    return pd.DataFrame(ls.numpy(), index=multi_index, columns=["score"])
+    return pd.DataFrame(ls.numpy(), index=multi_index, columns=cols)
 
 
 def RankIC(df: pd.DataFrame, column1: str = "LABEL0", column2: str = "Pred"):

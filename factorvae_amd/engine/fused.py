@@ -138,6 +138,16 @@ class FusedTrainer:
         # enc_fused_fwd kernels (bit-identical); FV_MID=0 restores the
         # original kernels
         self._mid = 0 if os.environ.get("FV_MID", "1") == "0" else 1
+        # every dtype, N <= 384: the training step's middle chain
+        # (docs/KERNELS.md): dec_fwd_bwd -> enc_bwd_mid on main with the loss
+        # gradients formed at their consumers, instead of dec_fwd ->
+        # loss_fused -> dec_bwd -> dec_bwd_reduce -> enc_bwd_fused
+        # (bit-identical); FV_MID_CHAIN=0 restores that sequence. Needs the
+        # latency-oriented attention backward, so FV_MID=0 turns it off too.
+        self._mid_chain = (self._mid == 1 and self.device.type == "cuda"
+                           and self.H <= 64 and self.K <= 128
+                           and os.environ.get("FV_MID_CHAIN", "1") != "0")
+        self._chain_pending = False
         if self.bf16:
             C3 = 3 * self.H
             # padded (+ transposed-padded) weight shadows for the
@@ -525,7 +535,11 @@ class FusedTrainer:
 
     # ------------------------------------------------------------ the step
     def _launch_forward(self, N: int, T: int, with_loss: bool = True,
-                        x=None, y=None):
+                        x=None, y=None, train: bool = False):
+        """Forward pass. train=True promises that _launch_backward follows:
+        where the middle chain applies, the forward then ends behind
+        enc_fused_fwd, and the decoder forward and the loss are launched
+        by _launch_backward as part of that chain."""
         ext, w, p = self.ext, self.ws, self.p
         C, H, M, K = self.C, self.H, self.M, self.K
         R = N * T
@@ -640,6 +654,9 @@ class FusedTrainer:
                               p("bsig_e"), w["fmu"], w["fsig_pre"],
                               w["fsig"], w["fsig_c"], w["enc_done"],
                               self._mid)
+            if train and with_loss and self._mid_chain and N <= 384:
+                self._chain_pending = True
+                return
         else:
             ext.gemm_nt(w["h"], p("Wenc"), p("benc"), w["scores_enc"], 1.0,
                         False, False)
@@ -699,6 +716,121 @@ class FusedTrainer:
         gq = self._gstack("q_att.0", (K, H))
         gWk = self._gstack("Wk.0", (K, H, H))
         gbk = self._gstack("bk.0", (K, H))
+        chain, self._chain_pending = self._chain_pending, False
+        if chain:
+            # dh_combine waits for the attention kernel only; the final
+            # join before Adam covers what follows it on that stream
+            main.wait_event(self._launch_mid_chain(
+                N, yv, mask, alpha, keep_inv, (gWv, gbv, gq, gWk, gbk)))
+        else:
+            self._launch_mid_old(N, yv, mask, alpha, keep_inv,
+                                 (gWv, gbv, gq, gWk, gbk))
+            self._join(1)
+        # ---- attention branch joined; assemble all three dh contributions
+        # (attention ds@qk + a@du, encoder dscores@Wenc) in ONE kernel
+        ext.dh_combine(w["dh"], w["ds"], w["qk"], w["a_att"], w["du"],
+                       w["dscores"], p("Wenc"))
+
+        if comm_overlap:
+            # every non-extractor gradient (arena tail from Wenc on) is
+            # final: reduce it now, overlapped with the extractor bwd
+            e1 = torch.cuda.Event()
+            e1.record(main)
+            self.s_comm.wait_event(e1)
+            for sstream in sides:
+                # the wgrads of the middle run on side 0, and with the
+                # middle chain the attention branch does too
+                if sstream is not None:
+                    e2 = torch.cuda.Event()
+                    e2.record(sstream)
+                    self.s_comm.wait_event(e2)
+            with torch.cuda.stream(self.s_comm):
+                tail = self.grads[self.params.offsets["Wenc"][0]:]
+                tail.div_(get_world_size())
+                torch.distributed.all_reduce(tail)
+
+        self._launch_extractor_bwd(N, T, x2d, chunks, main, sides,
+                                   comm_overlap)
+
+    def _launch_mid_chain(self, N, yv, mask, alpha, keep_inv, gatt):
+        """The middle of the training step as two critical-path nodes,
+        dec_fwd_bwd -> enc_bwd_mid (docs/KERNELS.md). _launch_forward
+        ended behind enc_fused_fwd. The loss gradients are formed where
+        they are used. The attention backward runs behind its forward on
+        side stream 0, followed there by what only Adam or the caller
+        needs: the decoder head-gradient reduce, the weight gradients and
+        the loss scalars. Returns the event dh_combine has to wait for."""
+        ext, w, p, g = self.ext, self.ws, self.p, self.g
+        gWv, gbv, gq, gWk, gbk = gatt
+        main = torch.cuda.current_stream(self.device)
+        s_att = self._streams()[0]
+        # fmu / fsig_c are ready (enc_fused_fwd) ...
+        e_enc = torch.cuda.Event()
+        e_enc.record(main)
+        # ... and pmu / psig_c behind attn_fused_fwd
+        e_att = torch.cuda.Event()
+        e_att.record(s_att)
+        # the critical-path successor of enc_fused_fwd is enqueued first:
+        # it keeps the hardware queue (profiles/f32_tail.md)
+        ext.dec_fwd_bwd(w["h"], p("W1d"), p("b1d"), p("wmu_d"), p("bmu_d"),
+                        p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"), w["fmu"],
+                        w["fsig_c"], w["eps"], yv, w["recon"], w["a1"],
+                        w["beta"], w["asig_pre"], w["sigma"], w["drecon"],
+                        w["dh"], w["dz1"], w["dbeta"], w["dec_part"], 1.0)
+        # attention backward: its forward's same-stream successor; head k
+        # forms dpmu / dpsig_c itself
+        s_att.wait_event(e_enc)
+        with torch.cuda.stream(s_att):
+            ext.attn_fused_bwd(w["dpmu"], w["dpsig_c"], w["psig"],
+                               w["psig_pre"], w["hm2"], p("wmu_p"),
+                               p("wsig_p"), p("Wl"), w["h"], w["a_att"],
+                               w["sd"], mask, w["guard"], w["u"],
+                               self.p_Wv, self.p_q, self.p_Wk, self.p_bk,
+                               w["dz2"], w["du"], w["ds"], w["dc"], gWv,
+                               gbv, gq, gWk, gbk, w["hpart"], g("wmu_p"),
+                               g("bmu_p"), g("wsig_p"), g("bsig_p"),
+                               alpha, keep_inv, self._mid, w["fmu"],
+                               w["fsig_c"], w["pmu"], w["psig_c"], 1.0)
+            e_join = torch.cuda.Event()
+            e_join.record(s_att)
+            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"))
+        # encoder backward, again enqueued before the side work: every
+        # workgroup sums the decoder's factor partials and adds the KL
+        # gradients itself
+        main.wait_event(e_att)
+        nblk = (N + 3) // 4
+        ext.enc_bwd_mid(w["dec_part"], nblk, w["fmu"], w["fsig_c"], w["pmu"],
+                        w["psig_c"], w["fsig"], w["fsig_pre"], w["yp"],
+                        p("Wmu_e"), p("Wsig_e"), w["a_enc"], yv,
+                        w["dscores"], g("Wmu_e"), g("bmu_e"), g("Wsig_e"),
+                        g("bsig_e"), w["dfmu"], w["dfsig_c"], 1.0)
+        e_encb = torch.cuda.Event()
+        e_encb.record(main)
+        # off the critical path, needed by Adam / the caller only: behind
+        # the attention branch on its stream, so the middle of the step
+        # stays at two concurrent branches. As a third branch this work
+        # shared a hardware queue with attn_fused_bwd and ran in front of
+        # it (profiles/mid_chain.md).
+        s_att.wait_event(e_encb)
+        with torch.cuda.stream(s_att):
+            ext.dec_bwd_reduce_heads(w["dec_part"], g("wmu_d"), g("bmu_d"),
+                                     g("wsig_d"), g("bsig_d"), N, self.K)
+            ext.gemm_tn(w["dz1"], w["h"], g("W1d"), w["tn_part_s"], 2, False,
+                        g("b1d"), w["tn_partb_s"])
+            ext.gemm_tn(w["dbeta"], w["h"], g("Wb"), w["tn_part_s"], 2, False,
+                        g("bb"), w["tn_partb_s"])
+            ext.loss_scalars(w["recon"], yv, w["fmu"], w["fsig_c"], w["pmu"],
+                             w["psig_c"], w["loss"], w["mse"], w["kl"])
+            ext.gemm_tn(w["dscores"], w["h"], g("Wenc"), w["tn_part_s"], 2,
+                        False, g("benc"), w["tn_partb_s"])
+        return e_join
+
+    def _launch_mid_old(self, N, yv, mask, alpha, keep_inv, gatt):
+        """The middle of the backward as separate kernels (FV_MID_CHAIN=0,
+        N > 384, or a forward that already ran dec_fwd and loss_fused)."""
+        ext, w, p, g = self.ext, self.ws, self.p, self.g
+        gWv, gbv, gq, gWk, gbk = gatt
+        fork, _on_side = self._fork, self._OnSide
         fork(1)
         with _on_side(self, 1):
             if N <= 384:
@@ -758,28 +890,12 @@ class FusedTrainer:
             ext.gemm_tn(w["dscores"], w["h"], g("Wenc"), w["tn_part_s"], 2,
                         False, g("benc"), w["tn_partb_s"])
 
-        # ---- join attention branch; assemble all three dh contributions
-        # (attention ds@qk + a@du, encoder dscores@Wenc) in ONE kernel
-        self._join(1)
-        ext.dh_combine(w["dh"], w["ds"], w["qk"], w["a_att"], w["du"],
-                       w["dscores"], p("Wenc"))
-
-        if comm_overlap:
-            # every non-extractor gradient (arena tail from Wenc on) is
-            # final: reduce it now, overlapped with the extractor bwd
-            e1 = torch.cuda.Event()
-            e1.record(main)
-            self.s_comm.wait_event(e1)
-            if sides[0] is not None:
-                e2 = torch.cuda.Event()
-                e2.record(sides[0])
-                self.s_comm.wait_event(e2)
-            with torch.cuda.stream(self.s_comm):
-                tail = self.grads[self.params.offsets["Wenc"][0]:]
-                tail.div_(get_world_size())
-                torch.distributed.all_reduce(tail)
-
-        # extractor backward
+    def _launch_extractor_bwd(self, N, T, x2d, chunks, main, sides,
+                              comm_overlap):
+        """GRU + projections + LayerNorm backward, and the final join."""
+        ext, w, p, g = self.ext, self.ws, self.p, self.g
+        H, R = self.H, N * T
+        fork, _on_side = self._fork, self._OnSide
         fp8_rs = self.fp8 and getattr(self, "_fp8_rs", False)
         fp8_gru_fused = fp8_rs and H == 64
         if fp8_rs:
@@ -1126,7 +1242,7 @@ class FusedTrainer:
             inc_early = True
         if rng_in_graph:
             self._fill_rng(N)
-        self._launch_forward(N, T, x=x, y=y)
+        self._launch_forward(N, T, x=x, y=y, train=True)
         self._launch_backward(N, T, x=x, y=y, comm_overlap=comm_in_graph)
         if comm_in_graph:
             # the non-extractor slice was reduced inside backward,
@@ -1154,7 +1270,7 @@ class FusedTrainer:
             with self._main_ctx():
                 self._fill_rng(N)
                 with roctx_range("fv_forward"):
-                    self._launch_forward(N, T)
+                    self._launch_forward(N, T, train=True)
                 with roctx_range("fv_backward"):
                     self._launch_backward(N, T)
                 if is_distributed():
@@ -1200,7 +1316,7 @@ class FusedTrainer:
             if not rng_ok:
                 self._fill_rng(N)
             self.grads.zero_()
-            self._launch_forward(N, T)
+            self._launch_forward(N, T, train=True)
             self._launch_backward(N, T)
         torch.cuda.synchronize()
 
@@ -1246,7 +1362,8 @@ class FusedTrainer:
             if not rng_ok:
                 self._fill_rng(N)
             self.grads.zero_()
-            self._launch_forward(N, T, x=days[0][0], y=days[0][1])
+            self._launch_forward(N, T, x=days[0][0], y=days[0][1],
+                                 train=True)
             self._launch_backward(N, T, x=days[0][0], y=days[0][1])
         torch.cuda.synchronize()
 
@@ -1636,7 +1753,7 @@ class FusedTrainer:
         torch.cuda.synchronize(self.device)
         with self._main_ctx():
             self._fill_rng(N)
-            self._launch_forward(N, T, x=xb[0], y=yb[0])
+            self._launch_forward(N, T, x=xb[0], y=yb[0], train=True)
             self._launch_backward(N, T, x=xb[0], y=yb[0])
         torch.cuda.synchronize(self.device)
         try:

@@ -915,7 +915,10 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_lat_kernel(
   MID_STAMP(6);
 }
 
-template <bool QUAD>
+// KLG (the middle chain, docs/KERNELS.md): head k forms its two KL
+// gradients itself with kl_grad_ from (fmu, fsig_c, pmu, psig_c)[k] and
+// stores them to dpmu / dpsig_c, instead of reading what loss_fused wrote.
+template <bool QUAD, bool KLG>
 __global__ __launch_bounds__(256) void attn_fused_bwd_lat_kernel(
     const float* __restrict__ dpmu, const float* __restrict__ dpsig_c,
     const float* __restrict__ psig, const float* __restrict__ psig_pre,
@@ -931,7 +934,11 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_lat_kernel(
     float* __restrict__ dWv, float* __restrict__ dbv,
     float* __restrict__ dq, float* __restrict__ dWk,
     float* __restrict__ dbk, float* __restrict__ hpart,
-    int N, int K, int H, float alpha, float keep_inv) {
+    int N, int K, int H, float alpha, float keep_inv,
+    const float* __restrict__ kl_fmu, const float* __restrict__ kl_fsig_c,
+    const float* __restrict__ kl_pmu, const float* __restrict__ kl_psig_c,
+    float kl_gscale, float* __restrict__ dpmu_out,
+    float* __restrict__ dpsig_c_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* hS = (float*)smem;               // [N][H+1]
   float* WlS = hS + (size_t)N * (H + 1);  // [H][H+1]: Wl, Wv, then Wk
@@ -967,9 +974,21 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_lat_kernel(
   const float wsig_r = wsig[tc];
   const float q_r = q[(long)k * H + tc];
   const float bk_r = bk[(long)k * H + tc];
-  const float dm = dpmu[k];
+  float dm, dpsig_ck;
+  if (KLG) {
+    const KlGrad kg = kl_grad_(kl_fmu[k], kl_fsig_c[k], kl_pmu[k],
+                               kl_psig_c[k], kl_gscale);
+    dm = kg.dpmu;
+    dpsig_ck = kg.dpsig_c;
+    if (tid == 0) {
+      dpmu_out[k] = dm;
+      dpsig_c_out[k] = dpsig_ck;
+    }
+  } else {
+    dm = dpmu[k];
+    dpsig_ck = dpsig_c[k];
+  }
   const float psig_k = psig[k];
-  const float dpsig_ck = dpsig_c[k];
   const float psig_pre_k = psig_pre[k];
   const int n0 = tid, n1 = tid + 256;
   const bool has0 = n0 < N, has1 = n1 < N;
@@ -1239,8 +1258,11 @@ hipError_t fv_attn_fused_bwd(const float* dpmu, const float* dpsig_c,
                              float* hpart, float* dwmu, float* dbmu,
                              float* dwsig, float* dbsig, int N, int K, int H,
                              float alpha, float keep_inv, int variant,
-                             hipStream_t s) {
+                             const float* kl_fmu, const float* kl_fsig_c,
+                             const float* kl_pmu, const float* kl_psig_c,
+                             float kl_gscale, hipStream_t s) {
   if (H > 64) return hipErrorInvalidValue;
+  // in-kernel KL gradients (kl_fmu given): dpmu / dpsig_c are outputs
   const size_t lds = ((size_t)N * (H + 1) + (size_t)H * (H + 1) + N + 8 +
                       256 + 5 * 64) * sizeof(float);
   if (lds > 128 * 1024) return hipErrorInvalidValue;
@@ -1248,19 +1270,25 @@ hipError_t fv_attn_fused_bwd(const float* dpmu, const float* dpsig_c,
   // N <= 512; two more 64-float LDS vectors); anything it does not cover
   // runs the original kernel, as variant 0 does
   const size_t lds_lat = lds + 2 * 64 * sizeof(float);
-  if (variant != 0 && N <= 512 && lds_lat <= 128 * 1024) {
-    if (H % 4 == 0)
-      hipLaunchKernelGGL(attn_fused_bwd_lat_kernel<true>, dim3(K), dim3(256),
-                         lds_lat, s, dpmu, dpsig_c, psig, psig_pre, hm2, wmu,
-                         wsig, Wl, h, a, sd, mask, guard, u, Wv, q, Wk, bk,
-                         dz2, du, ds, dc, dWv, dbv, dq, dWk, dbk, hpart, N, K,
-                         H, alpha, keep_inv);
-    else
-      hipLaunchKernelGGL(attn_fused_bwd_lat_kernel<false>, dim3(K), dim3(256),
-                         lds_lat, s, dpmu, dpsig_c, psig, psig_pre, hm2, wmu,
-                         wsig, Wl, h, a, sd, mask, guard, u, Wv, q, Wk, bk,
-                         dz2, du, ds, dc, dWv, dbv, dq, dWk, dbk, hpart, N, K,
-                         H, alpha, keep_inv);
+  const bool lat = variant != 0 && N <= 512 && lds_lat <= 128 * 1024;
+  // only the latency-oriented kernel forms the KL gradients itself
+  if (kl_fmu && !lat) return hipErrorInvalidValue;
+#define ATTN_BWD_LAT(QUAD, KLG)                                              \
+  hipLaunchKernelGGL((attn_fused_bwd_lat_kernel<QUAD, KLG>), dim3(K),        \
+                     dim3(256), lds_lat, s, dpmu, dpsig_c, psig, psig_pre,   \
+                     hm2, wmu, wsig, Wl, h, a, sd, mask, guard, u, Wv, q,    \
+                     Wk, bk, dz2, du, ds, dc, dWv, dbv, dq, dWk, dbk, hpart, \
+                     N, K, H, alpha, keep_inv, kl_fmu, kl_fsig_c, kl_pmu,    \
+                     kl_psig_c, kl_gscale, (float*)dpmu, (float*)dpsig_c)
+  if (lat) {
+    if (H % 4 == 0) {
+      if (kl_fmu) ATTN_BWD_LAT(true, true);
+      else ATTN_BWD_LAT(true, false);
+    } else {
+      if (kl_fmu) ATTN_BWD_LAT(false, true);
+      else ATTN_BWD_LAT(false, false);
+    }
+#undef ATTN_BWD_LAT
   } else {
     hipLaunchKernelGGL(attn_fused_bwd_kernel, dim3(K), dim3(256), lds, s,
                        dpmu, dpsig_c, psig, psig_pre, hm2, wmu, wsig, Wl, h,

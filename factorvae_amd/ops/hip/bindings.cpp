@@ -122,7 +122,27 @@ hipError_t fv_attn_fused_bwd(const float*, const float*, const float*,
                              float*, float*, float*, float*, float*, float*,
                              float*, float*, float*, float*, float*, float*,
                              float*, float*, int, int, int, float, float,
-                             int, hipStream_t);
+                             int, const float*, const float*, const float*,
+                             const float*, float, hipStream_t);
+// the training step's middle chain (docs/KERNELS.md)
+hipError_t fv_dec_fwd_bwd(const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, float*, float*, float*, float*,
+                          float*, float*, float*, float*, float*, float*, int,
+                          int, int, float, hipStream_t);
+hipError_t fv_dec_bwd_reduce_heads(const float*, float*, float*, float*,
+                                   float*, int, int, int, hipStream_t);
+hipError_t fv_enc_bwd_mid(const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*,
+                          const float*, const float*, const float*, float*,
+                          float*, float*, float*, float*, float*, float*, int,
+                          int, int, int, float, hipStream_t);
+hipError_t fv_loss_scalars(const float*, const float*, const float*,
+                           const float*, const float*, const float*, float*,
+                           float*, float*, int, int, hipStream_t);
 hipError_t fv_attn_fused_fwd(const float*, const float*, const float*,
                              const float*, const float*, const float*,
                              const float*, const float*, const float*,
@@ -882,7 +902,12 @@ void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
                     torch::Tensor hpart,
                     torch::Tensor dwmu, torch::Tensor dbmu,
                     torch::Tensor dwsig, torch::Tensor dbsig,
-                    double alpha, double keep_inv, int variant) {
+                    double alpha, double keep_inv, int variant,
+                    c10::optional<torch::Tensor> kl_fmu = c10::nullopt,
+                    c10::optional<torch::Tensor> kl_fsig_c = c10::nullopt,
+                    c10::optional<torch::Tensor> kl_pmu = c10::nullopt,
+                    c10::optional<torch::Tensor> kl_psig_c = c10::nullopt,
+                    double kl_gscale = 1.0) {
   CK(h); CK(a); CK(sd); CK(u); CK(Wv); CK(q); CK(Wk); CK(bk); CK(dz2);
   CK(du); CK(ds); CK(dc); CK(dWv); CK(dbv); CK(dq); CK(dWk); CK(dbk);
   CK(hpart);
@@ -890,6 +915,21 @@ void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
   TORCH_CHECK(hpart.numel() >= (long)K * (2 * H + 2));
   const float* mp = nullptr;
   if (mask.has_value()) { CK(*mask); mp = fp(*mask); }
+  // in-kernel KL gradients: all four inputs or none; dpmu and dpsig_c
+  // are then outputs
+  const float* kfm = nullptr; const float* kfs = nullptr;
+  const float* kpm = nullptr; const float* kps = nullptr;
+  if (kl_fmu.has_value()) {
+    TORCH_CHECK(kl_fsig_c.has_value() && kl_pmu.has_value() &&
+                kl_psig_c.has_value(), "kl_* come as a set of four");
+    CK(*kl_fmu); CK(*kl_fsig_c); CK(*kl_pmu); CK(*kl_psig_c);
+    CK(dpmu); CK(dpsig_c);
+    TORCH_CHECK(kl_fmu->numel() >= K && kl_fsig_c->numel() >= K &&
+                kl_pmu->numel() >= K && kl_psig_c->numel() >= K &&
+                dpmu.numel() >= K && dpsig_c.numel() >= K, "kl_* sizes");
+    kfm = fp(*kl_fmu); kfs = fp(*kl_fsig_c);
+    kpm = fp(*kl_pmu); kps = fp(*kl_psig_c);
+  }
   RUN(fv_attn_fused_bwd(fp(dpmu), fp(dpsig_c), fp(psig), fp(psig_pre),
                         fp(hm2), fp(wmu), fp(wsig), fp(Wl), fp(h), fp(a),
                         fp(sd), mp, guard.data_ptr<int>(), fp(u), fp(Wv),
@@ -897,7 +937,8 @@ void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
                         fpm(dc), fpm(dWv), fpm(dbv), fpm(dq), fpm(dWk),
                         fpm(dbk), fpm(hpart), fpm(dwmu), fpm(dbmu),
                         fpm(dwsig), fpm(dbsig), N, K, H, (float)alpha,
-                        (float)keep_inv, variant, cur_stream()));
+                        (float)keep_inv, variant, kfm, kfs, kpm, kps,
+                        (float)kl_gscale, cur_stream()));
 }
 
 void enc_fused_fwd(torch::Tensor h, torch::Tensor Wenc, torch::Tensor benc,
@@ -1243,6 +1284,106 @@ void loss_fused(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
                     recon.numel(), fmu.numel(), (float)gscale, cur_stream()));
 }
 
+// ---- the training step's middle chain --------------------------------
+inline long dec_nblk(long N) {
+  long iters = (N + 4 * 128 - 1) / (4 * 128);
+  if (iters > 8) iters = 8;
+  if (iters < 1) iters = 1;
+  return (N + 4 * iters - 1) / (4 * iters);
+}
+
+void dec_fwd_bwd(torch::Tensor h, torch::Tensor W1, torch::Tensor b1,
+                 torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
+                 torch::Tensor bsig, torch::Tensor Wb, torch::Tensor bb,
+                 torch::Tensor fmu, torch::Tensor fsig_c, torch::Tensor eps,
+                 torch::Tensor y, torch::Tensor recon, torch::Tensor a1,
+                 torch::Tensor beta, torch::Tensor asig_pre,
+                 torch::Tensor sigma, torch::Tensor drecon, torch::Tensor dh,
+                 torch::Tensor dz1, torch::Tensor dbeta, torch::Tensor part,
+                 double gscale) {
+  CK(h); CK(W1); CK(b1); CK(wmu); CK(bmu); CK(wsig); CK(bsig); CK(Wb); CK(bb);
+  CK(fmu); CK(fsig_c); CK(eps); CK(y); CK(recon); CK(a1); CK(beta);
+  CK(asig_pre); CK(sigma); CK(drecon); CK(dh); CK(dz1); CK(dbeta); CK(part);
+  const long N = h.size(0), H = h.size(1), K = Wb.size(0);
+  TORCH_CHECK(H >= 1 && H <= 64 && K >= 1 && K <= 128 && N >= 1,
+              "dec_fwd_bwd: H <= 64, K <= 128");
+  TORCH_CHECK(W1.numel() == H * H && Wb.numel() == K * H && b1.numel() >= H &&
+              wmu.numel() >= H && wsig.numel() >= H && bb.numel() >= K &&
+              fmu.numel() >= K && fsig_c.numel() >= K && bmu.numel() >= 1 &&
+              bsig.numel() >= 1, "dec_fwd_bwd: parameter sizes");
+  TORCH_CHECK(eps.numel() >= N && y.numel() >= N && recon.numel() >= N &&
+              asig_pre.numel() >= N && sigma.numel() >= N &&
+              drecon.numel() >= N && a1.numel() >= N * H &&
+              dh.numel() >= N * H && dz1.numel() >= N * H &&
+              beta.numel() >= N * K && dbeta.numel() >= N * K,
+              "dec_fwd_bwd: row buffer sizes");
+  TORCH_CHECK(part.numel() >= dec_nblk(N) * (2 * K + 2 * H + 2));
+  RUN(fv_dec_fwd_bwd(fp(h), fp(W1), fp(b1), fp(wmu), fp(bmu), fp(wsig),
+                     fp(bsig), fp(Wb), fp(bb), fp(fmu), fp(fsig_c), fp(eps),
+                     fp(y), fpm(recon), fpm(a1), fpm(beta), fpm(asig_pre),
+                     fpm(sigma), fpm(drecon), fpm(dh), fpm(dz1), fpm(dbeta),
+                     fpm(part), (int)N, (int)K, (int)H, (float)gscale,
+                     cur_stream()));
+}
+
+// the 2H+2 decoder head gradients out of dec_fwd_bwd's partials (N rows)
+void dec_bwd_reduce_heads(torch::Tensor part, torch::Tensor dwmu,
+                          torch::Tensor dbmu, torch::Tensor dwsig,
+                          torch::Tensor dbsig, long N, long K) {
+  CK(part); CK(dwmu); CK(dbmu); CK(dwsig); CK(dbsig);
+  const long H = dwmu.numel();
+  TORCH_CHECK(dwsig.numel() == H && dbmu.numel() >= 1 && dbsig.numel() >= 1);
+  TORCH_CHECK(N >= 1 && K >= 1 &&
+              part.numel() >= dec_nblk(N) * (2 * K + 2 * H + 2));
+  RUN(fv_dec_bwd_reduce_heads(fp(part), fpm(dwmu), fpm(dbmu), fpm(dwsig),
+                              fpm(dbsig), (int)N, (int)K, (int)H,
+                              cur_stream()));
+}
+
+// enc_bwd_fused that forms dfmu / dfsig_c itself from the KL inputs and the
+// decoder's nblk block partials; dfmu and dfsig_c are outputs
+void enc_bwd_mid(torch::Tensor part, long nblk, torch::Tensor fmu,
+                 torch::Tensor fsig_c, torch::Tensor pmu,
+                 torch::Tensor psig_c, torch::Tensor fsig,
+                 torch::Tensor fsig_pre, torch::Tensor yp, torch::Tensor Wmu,
+                 torch::Tensor Wsig, torch::Tensor a, torch::Tensor y,
+                 torch::Tensor dscores, torch::Tensor dWmu,
+                 torch::Tensor dbmu, torch::Tensor dWsig, torch::Tensor dbsig,
+                 torch::Tensor dfmu, torch::Tensor dfsig_c, double gscale) {
+  CK(part); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(fsig); CK(fsig_pre);
+  CK(yp); CK(Wmu); CK(Wsig); CK(a); CK(y); CK(dscores); CK(dWmu); CK(dbmu);
+  CK(dWsig); CK(dbsig); CK(dfmu); CK(dfsig_c);
+  const long N = a.size(0), M = a.size(1), K = Wmu.size(0);
+  TORCH_CHECK(K >= 1 && K <= 256 && nblk >= 1 && M >= 1,
+              "enc_bwd_mid: K <= 256");
+  TORCH_CHECK(part.numel() >= 2 * K * nblk, "enc_bwd_mid: part size");
+  TORCH_CHECK(fmu.numel() >= K && fsig_c.numel() >= K && pmu.numel() >= K &&
+              psig_c.numel() >= K && fsig.numel() >= K &&
+              fsig_pre.numel() >= K && dfmu.numel() >= K &&
+              dfsig_c.numel() >= K && dbmu.numel() >= K &&
+              dbsig.numel() >= K && yp.numel() >= M && y.numel() >= N &&
+              Wmu.numel() == K * M && Wsig.numel() == K * M &&
+              dWmu.numel() >= K * M && dWsig.numel() >= K * M &&
+              dscores.numel() >= N * M, "enc_bwd_mid: sizes");
+  RUN(fv_enc_bwd_mid(fp(part), fp(fmu), fp(fsig_c), fp(pmu), fp(psig_c),
+                     fp(fsig), fp(fsig_pre), fp(yp), fp(Wmu), fp(Wsig), fp(a),
+                     fp(y), fpm(dscores), fpm(dWmu), fpm(dbmu), fpm(dWsig),
+                     fpm(dbsig), fpm(dfmu), fpm(dfsig_c), (int)nblk, (int)N,
+                     (int)M, (int)K, (float)gscale, cur_stream()));
+}
+
+// loss, mse and kl only (loss_fused without its gradient stores)
+void loss_scalars(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
+                  torch::Tensor fsig_c, torch::Tensor pmu,
+                  torch::Tensor psig_c, torch::Tensor loss, torch::Tensor mse,
+                  torch::Tensor kl) {
+  CK(recon); CK(y); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(loss);
+  CK(mse); CK(kl);
+  RUN(fv_loss_scalars(fp(recon), fp(y), fp(fmu), fp(fsig_c), fp(pmu),
+                      fp(psig_c), fpm(loss), fpm(mse), fpm(kl), recon.numel(),
+                      fmu.numel(), cur_stream()));
+}
+
 void dh_combine(torch::Tensor dh, torch::Tensor ds, torch::Tensor qk,
                 torch::Tensor a, torch::Tensor du, torch::Tensor dscores,
                 torch::Tensor Wenc) {
@@ -1357,7 +1498,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("dbk"), py::arg("hpart"), py::arg("dwmu"), py::arg("dbmu"),
           py::arg("dwsig"), py::arg("dbsig"), py::arg("alpha"),
           py::arg("keep_inv"),
-          py::arg("variant") = 1);
+          py::arg("variant") = 1, py::arg("kl_fmu") = py::none(),
+          py::arg("kl_fsig_c") = py::none(), py::arg("kl_pmu") = py::none(),
+          py::arg("kl_psig_c") = py::none(), py::arg("kl_gscale") = 1.0);
+  mod.def("dec_fwd_bwd", &dec_fwd_bwd);
+  mod.def("dec_bwd_reduce_heads", &dec_bwd_reduce_heads);
+  mod.def("enc_bwd_mid", &enc_bwd_mid);
+  mod.def("loss_scalars", &loss_scalars);
   mod.def("gru_bwd_mfma", &gru_bwd_mfma, py::arg("dh_final"),
           py::arg("h_prev"), py::arg("gates4"), py::arg("whh_bf"),
           py::arg("dgi"), py::arg("dgh"), py::arg("N"), py::arg("T"),

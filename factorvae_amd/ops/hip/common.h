@@ -83,7 +83,51 @@ DEVINL float block_reduce_max(float v, float* scratch) {
   return block_reduce(v, scratch, MaxOp{}, -INFINITY);
 }
 
-#define HIP_CHECK_LAST()                                    \
+// a + b as its own rounding step: never contracted with a multiply that
+// produced a or b. Used where the original sequence stored the product
+// to memory and added to it in a later kernel.
+DEVINL float add_rn_(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// The four KL input-gradients of one factor, exactly loss_fused_kernel's
+// expressions (loss.hip), for consumers that form them in place. Compiled
+// without contraction: loss_fused_kernel rounds both squares of
+// fs*fs + dmu*dmu before it adds them (the compiler pairs the two
+// multiplies into one packed instruction there), and nothing else in
+// these expressions has a multiply feeding an add.
+struct KlGrad {
+  float dfmu, dfsig_c, dpmu, dpsig_c;
+};
+DEVINL KlGrad kl_grad_(float fm, float fs, float pm, float ps, float gscale) {
+#pragma clang fp contract(off)
+  const float dmu = fm - pm;
+  const float ps2 = ps * ps;
+  KlGrad g;
+  g.dfmu = gscale * dmu / ps2;
+  g.dfsig_c = gscale * (-1.0f / fs + fs / ps2);
+  g.dpmu = gscale * (-dmu / ps2);
+  g.dpsig_c = gscale * (1.0f / ps - (fs * fs + dmu * dmu) / (ps2 * ps));
+  return g;
+}
+
+// One lane's share of dec_bwd_reduce_kernel's fixed-order sum over the
+// nblk block partials of one element: lane l takes partials l, l+64, ...
+// into two accumulators; wave_reduce_sum of the result is the element's sum.
+DEVINL float dec_part_lane_sum_(const float* __restrict__ pe, int nblk,
+                                int lane) {
+  float s0 = 0.f, s1 = 0.f;
+  int z = lane;
+  for (; z + 64 < nblk; z += 128) {
+    s0 += pe[z];
+    s1 += pe[z + 64];
+  }
+  if (z < nblk) s0 += pe[z];
+  return s0 + s1;
+}
+
+#define HIP_CHECK_LAST()                                  \
   do {                                                      \
     hipError_t e_ = hipGetLastError();                      \
     if (e_ != hipSuccess) return e_;                        \

@@ -442,6 +442,136 @@ __global__ __launch_bounds__(256) void enc_bwd_fused_kernel(
   }
 }
 
+// enc_bwd_fused_kernel for the middle chain (docs/KERNELS.md): every
+// workgroup first forms the final dfmu / dfsig_c itself, as loss_fused's KL
+// gradient (kl_grad_) plus dec_bwd_reduce_kernel's fixed-order sum of the
+// decoder's block partials (one wave per element, lane l sums partials l,
+// l+64, ..., then wave_reduce_sum), and then runs enc_bwd_fused_kernel's
+// body. 2K sums of nblk floats per workgroup, instead of a loss_fused and
+// a dec_bwd_reduce node in front of this one. Workgroup 0 stores the final
+// dfmu and dfsig_c. One factor per thread: K <= 256.
+#define ENC_MID_NJ 10
+__global__ __launch_bounds__(256) void enc_bwd_mid_kernel(
+    const float* __restrict__ part, const float* __restrict__ fmu,
+    const float* __restrict__ fsig_c, const float* __restrict__ pmu,
+    const float* __restrict__ psig_c, const float* __restrict__ fsig,
+    const float* __restrict__ fsig_pre, const float* __restrict__ yp,
+    const float* __restrict__ Wmu, const float* __restrict__ Wsig,
+    const float* __restrict__ a, const float* __restrict__ y,
+    float* __restrict__ dscores, float* __restrict__ dWmu,
+    float* __restrict__ dbmu, float* __restrict__ dWsig,
+    float* __restrict__ dbsig, float* __restrict__ dfmu_out,
+    float* __restrict__ dfsig_c_out, int nblk, int N, int M, int K,
+    float gscale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* dmuS = (float*)smem;      // [K]
+  float* dsigS = dmuS + K;         // [K]
+  float* scratch = dsigS + K;      // [8]
+  float* sS = scratch + 8;         // [2K] decoder partial sums
+  __shared__ float dypS;
+
+  const int m = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int E2 = 2 * K;
+
+  // this thread's factor (clamped: threads >= K drop the result)
+  const int kc = min(tid, K - 1);
+  const KlGrad kg =
+      kl_grad_(fmu[kc], fsig_c[kc], pmu[kc], psig_c[kc], gscale);
+  const float fsig_k = fsig[kc];
+  const float fsig_pre_k = fsig_pre[kc];
+  const float yp_m = yp[m];
+
+  // ---- the 2K partial sums; wave w takes elements w, w+4, ...
+  for (int j0 = 0; w + 4 * j0 < E2; j0 += ENC_MID_NJ) {
+    float v[ENC_MID_NJ];
+    if (nblk <= 128) {
+      // dec_part_lane_sum_ with its at most one loop trip written out, so
+      // that all of a round's loads are in flight together
+      const bool one = lane < nblk, two = lane + 64 < nblk;
+      const int z0 = one ? lane : 0, z1 = two ? lane + 64 : 0;
+      float p0[ENC_MID_NJ], p1[ENC_MID_NJ];
+#pragma unroll
+      for (int jj = 0; jj < ENC_MID_NJ; ++jj) {
+        const int e = min(w + 4 * (j0 + jj), E2 - 1);
+        const float* pe = part + (long)e * nblk;
+        p0[jj] = pe[z0];
+        p1[jj] = pe[z1];
+      }
+#pragma unroll
+      for (int jj = 0; jj < ENC_MID_NJ; ++jj) {
+        float s0 = 0.f, s1 = 0.f;
+        if (two) {
+          s0 += p0[jj];
+          s1 += p1[jj];
+        } else if (one) {
+          s0 += p0[jj];
+        }
+        v[jj] = s0 + s1;
+      }
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < ENC_MID_NJ; ++jj) {
+        const int e = min(w + 4 * (j0 + jj), E2 - 1);
+        v[jj] = dec_part_lane_sum_(part + (long)e * nblk, nblk, lane);
+      }
+    }
+    wave_reduce_sum_n<ENC_MID_NJ>(v);
+    if (lane == 0) {
+#pragma unroll
+      for (int jj = 0; jj < ENC_MID_NJ; ++jj) {
+        const int e = w + 4 * (j0 + jj);
+        if (e < E2) sS[e] = v[jj];
+      }
+    }
+  }
+  __syncthreads();
+
+  if (tid < K) {
+    const int k = tid;
+    // loss_fused stored the KL gradient and dec_bwd_reduce added the sum
+    const float dm = add_rn_(kg.dfmu, sS[k]);
+    const float dfs = add_rn_(kg.dfsig_c, sS[K + k]);
+    const float dsc = (fsig_k == 0.0f) ? 0.0f : dfs;
+    const float dsg = dsc * softplus_gradf_(fsig_pre_k);
+    dmuS[k] = dm;
+    dsigS[k] = dsg;
+    dWmu[(long)k * M + m] = dm * yp_m;
+    dWsig[(long)k * M + m] = dsg * yp_m;
+    if (m == 0) {
+      dbmu[k] = dm;
+      dbsig[k] = dsg;
+      dfmu_out[k] = dm;
+      dfsig_c_out[k] = dfs;
+    }
+  }
+  __syncthreads();
+
+  // dyp[m] = sum_k dmu[k]*Wmu[k][m] + dsig[k]*Wsig[k][m]
+  if (tid == 0) {
+    float acc = 0.0f;
+    for (int k = 0; k < K; ++k)
+      acc += dmuS[k] * Wmu[(long)k * M + m] + dsigS[k] * Wsig[(long)k * M + m];
+    dypS = acc;
+  }
+  __syncthreads();
+  const float g = dypS;
+
+  float t = 0.0f;
+  for (int n = tid; n < N; n += 256) {
+    const float an = a[(long)n * M + m];
+    t = fmaf(an, g * y[n], t);
+  }
+  t = block_reduce_sum(t, scratch);
+
+  for (int n = tid; n < N; n += 256) {
+    const float an = a[(long)n * M + m];
+    dscores[(long)n * M + m] = an * (g * y[n] - t);
+  }
+}
+
 // yp (M) -> fmu (K), fsig_pre (K), fsig (K), fsig_c (K) (the decoder's
 // in-place ==0 -> 1e-6 clamp, module.py:117). One workgroup.
 __global__ __launch_bounds__(256) void enc_heads_fwd_kernel(
@@ -520,6 +650,25 @@ hipError_t fv_enc_bwd_fused(const float* dfmu, const float* dfsig_c,
   hipLaunchKernelGGL(enc_bwd_fused_kernel, dim3(M), dim3(256), lds, s,
                      dfmu, dfsig_c, fsig, fsig_pre, yp, Wmu, Wsig, a, y,
                      dscores, dWmu, dbmu, dWsig, dbsig, N, M, K);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_enc_bwd_mid(const float* part, const float* fmu,
+                          const float* fsig_c, const float* pmu,
+                          const float* psig_c, const float* fsig,
+                          const float* fsig_pre, const float* yp,
+                          const float* Wmu, const float* Wsig, const float* a,
+                          const float* y, float* dscores, float* dWmu,
+                          float* dbmu, float* dWsig, float* dbsig,
+                          float* dfmu, float* dfsig_c, int nblk, int N, int M,
+                          int K, float gscale, hipStream_t s) {
+  if (K < 1 || K > 256 || nblk < 1 || M < 1) return hipErrorInvalidValue;
+  const size_t lds = ((size_t)4 * K + 8) * sizeof(float);
+  hipLaunchKernelGGL(enc_bwd_mid_kernel, dim3(M), dim3(256), lds, s, part,
+                     fmu, fsig_c, pmu, psig_c, fsig, fsig_pre, yp, Wmu, Wsig,
+                     a, y, dscores, dWmu, dbmu, dWsig, dbsig, dfmu, dfsig_c,
+                     nblk, N, M, K, gscale);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -65,7 +65,11 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(
 // ONE launch (the backward math of loss_bwd_kernel needs nothing the
 // forward didn't already read, so splitting them was pure dispatch +
 // re-read cost on the critical path). Single workgroup; N and K loops
-// strided by 256.
+// strided by 256. GRAD = false drops the five gradient stores (the middle
+// chain forms those gradients at their consumers and launches this kernel
+// off the critical path for the three scalars only); the reductions are
+// the same, so loss, mse and kl keep their bits.
+template <bool GRAD>
 __global__ __launch_bounds__(256) void loss_fused_kernel(
     const float* __restrict__ recon, const float* __restrict__ y,
     const float* __restrict__ fmu, const float* __restrict__ fsig_c,
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256) void loss_fused_kernel(
   for (int n = tid; n < N; n += 256) {
     const float d = recon[n] - y[n];
     se = fmaf(d, d, se);
-    drecon[n] = dscale * d;
+    if (GRAD) drecon[n] = dscale * d;
   }
   se = block_reduce_sum(se, scratch);
   const float mse = se / N;
@@ -94,10 +98,12 @@ __global__ __launch_bounds__(256) void loss_fused_kernel(
     const float dmu = fmu[k] - pmu[k];
     const float ps2 = ps * ps;
     kl += __logf(ps / fs) + (fs * fs + dmu * dmu) / (2.0f * ps2) - 0.5f;
-    dfmu[k] = gscale * dmu / ps2;
-    dfsig_c[k] = gscale * (-1.0f / fs + fs / ps2);
-    dpmu[k] = gscale * (-dmu / ps2);
-    dpsig_c[k] = gscale * (1.0f / ps - (fs * fs + dmu * dmu) / (ps2 * ps));
+    if (GRAD) {
+      dfmu[k] = gscale * dmu / ps2;
+      dfsig_c[k] = gscale * (-1.0f / fs + fs / ps2);
+      dpmu[k] = gscale * (-dmu / ps2);
+      dpsig_c[k] = gscale * (1.0f / ps - (fs * fs + dmu * dmu) / (ps2 * ps));
+    }
   }
   kl = block_reduce_sum(kl, scratch);
 
@@ -116,9 +122,23 @@ hipError_t fv_loss_fused(const float* recon, const float* y, const float* fmu,
                          float* kl, float* drecon, float* dfmu,
                          float* dfsig_c, float* dpmu, float* dpsig_c, int N,
                          int K, float gscale, hipStream_t s) {
-  hipLaunchKernelGGL(loss_fused_kernel, dim3(1), dim3(256), 0, s, recon, y,
-                     fmu, fsig_c, pmu, psig_c, loss, mse, kl, drecon, dfmu,
+  hipLaunchKernelGGL(loss_fused_kernel<true>, dim3(1), dim3(256), 0, s, recon,
+                     y, fmu, fsig_c, pmu, psig_c, loss, mse, kl, drecon, dfmu,
                      dfsig_c, dpmu, dpsig_c, N, K, gscale);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// the three loss scalars only (loss_fused_kernel<false>)
+hipError_t fv_loss_scalars(const float* recon, const float* y,
+                           const float* fmu, const float* fsig_c,
+                           const float* pmu, const float* psig_c, float* loss,
+                           float* mse, float* kl, int N, int K,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(loss_fused_kernel<false>, dim3(1), dim3(256), 0, s,
+                     recon, y, fmu, fsig_c, pmu, psig_c, loss, mse, kl,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                     (float*)nullptr, (float*)nullptr, N, K, 1.0f);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

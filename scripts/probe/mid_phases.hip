@@ -168,7 +168,7 @@ int main(int argc, char** argv) {
                            h, a, sd, mask, guard, u, Wv, q, Wk, bk, dz2, du,
                            ds, dc, dWv, dbv, dq, dWk, dbk, hpart, dwmu, dbmu,
                            dwsig, dbsig, N, K, H, alpha, keep_inv, variant,
-                           0));
+                           nullptr, nullptr, nullptr, nullptr, 1.0f, 0));
     });
   }
   for (int variant = 0; variant < 2; ++variant) {

@@ -1540,6 +1540,7 @@ class FusedTrainer:
             iw["eps"] = f(Nn)
             iw["out"] = f(3, Nn)  # rows: sample, mu, sigma
             iw.pop("beta", None)
+            iw.pop("label", None)
             iw["N"] = Nn
         if with_beta and "beta" not in iw:
             iw["beta"] = f(iw["N"], K)
@@ -1625,19 +1626,47 @@ class FusedTrainer:
         batched with. Uses a dedicated inference workspace: training
         buffers, the shape/graph cache and the in-graph RNG state are not
         touched (with eps=None the generator advances, as in predict)."""
-        if self.fp8:
-            raise ValueError("predict_many supports the fp32 and bf16 "
-                             "engines; fp8 scoring is not implemented")
-        if self.K > 128:
-            raise UnsupportedShapeError(
-                f"predict_many supports num_factor <= 128, got {self.K}")
         xs = list(xs)
         if eps is not None:
             eps = list(eps)
+        results = [None] * len(xs)
+        for idxs, lens, offs, iw in self._pm_chunks(
+                "predict_many", xs, eps, max_rows, return_beta):
+            if iw is None:
+                for i in idxs:
+                    results[i] = self._pm_entry(
+                        torch.empty(3, 0), torch.empty(0, self.K), 0, 0,
+                        return_dist, return_beta)
+                continue
+            Nn = offs[-1]
+            out = iw["out"][:, :Nn].cpu()  # the chunk's one D2H copy
+            beta = iw["beta"][:Nn].cpu() if return_beta else None
+            for i, o, n in zip(idxs, offs, lens):
+                results[i] = self._pm_entry(out, beta, o, n, return_dist,
+                                            return_beta)
+        return results
+
+    def _pm_chunks(self, what: str, xs, eps, max_rows, with_beta: bool,
+                   ys=None, draw_eps: bool = True):
+        """The chunk/pack loop shared by predict_many and evaluate_many:
+        checks the days, packs them greedily into chunks within max_rows,
+        and for each chunk copies the inputs into the inference workspace,
+        runs the kernel sequence and yields (idxs, lens, offs, iw) with
+        the results still on the device. A chunk without any row yields
+        iw = None and launches nothing. ys: optional per-day labels, packed
+        into iw["label"]. draw_eps=False zero-fills a missing eps instead
+        of drawing it, leaving torch's generator alone."""
+        if self.fp8:
+            raise ValueError(f"{what} supports the fp32 and bf16 "
+                             "engines; fp8 scoring is not implemented")
+        if self.K > 128:
+            raise UnsupportedShapeError(
+                f"{what} supports num_factor <= 128, got {self.K}")
+        if eps is not None:
             if len(eps) != len(xs):
                 raise ValueError("eps must hold one (N_d,) tensor per day")
         if not xs:
-            return []
+            return
         T = xs[0].shape[1]
         for i, x in enumerate(xs):
             if x.ndim != 3 or x.shape[1] != T or x.shape[2] != self.C:
@@ -1647,6 +1676,9 @@ class FusedTrainer:
             if eps is not None and eps[i].numel() != x.shape[0]:
                 raise ValueError(f"day {i}: eps must have {x.shape[0]} "
                                  f"entries, got {eps[i].numel()}")
+            if ys is not None and ys[i].numel() != x.shape[0]:
+                raise ValueError(f"day {i}: labels must have {x.shape[0]} "
+                                 f"entries, got {ys[i].numel()}")
         if max_rows is None:
             max_rows = (int(os.environ.get("FV_PREDICT_ROWS", "0"))
                         or self.PREDICT_ROWS)
@@ -1665,26 +1697,22 @@ class FusedTrainer:
         # everything below runs on the caller's stream: order it after any
         # training step still in flight on the priority stream
         self._main_exit()
-        results = [None] * len(xs)
         qk_done = False
         for idxs in chunks:
             lens = [xs[i].shape[0] for i in idxs]
             Nn, D = sum(lens), len(idxs)
             R = Nn * T
+            offs = [0]
+            for n in lens:
+                offs.append(offs[-1] + n)
             if Nn == 0:
-                for i in idxs:
-                    results[i] = self._pm_entry(
-                        torch.empty(3, 0), torch.empty(0, self.K), 0, 0,
-                        return_dist, return_beta)
+                yield idxs, lens, offs, None
                 continue
-            iw = self._alloc_infer_ws(R, Nn, D, return_beta)
+            iw = self._alloc_infer_ws(R, Nn, D, with_beta)
             if not qk_done:
                 ext.attn_qk_fwd(self.p_q, self.p_Wk, self.p_bk, iw["qk"],
                                 iw["cb"])
                 qk_done = True
-            offs = [0]
-            for n in lens:
-                offs.append(offs[-1] + n)
             iw["seg_off"][:D + 1].copy_(
                 torch.tensor(offs, dtype=torch.int32), non_blocking=False)
             xd = iw["x"][:R]
@@ -1699,24 +1727,33 @@ class FusedTrainer:
                 for t, o, n in zip(flat, offs, lens):
                     xd[o * T:(o + n) * T].copy_(t)
             if eps is None:
-                iw["eps"][:Nn].normal_()
-            else:
-                e_host = [eps[i].reshape(-1).float() for i in idxs]
-                if all(t.device.type == "cpu" for t in e_host):
-                    iw["eps"][:Nn].copy_(torch.cat(e_host))
-                elif all(t.device == xd.device for t in e_host):
-                    torch.cat(e_host, out=iw["eps"][:Nn])
+                if draw_eps:
+                    iw["eps"][:Nn].normal_()
                 else:
-                    for t, o, n in zip(e_host, offs, lens):
-                        iw["eps"][o:o + n].copy_(t)
-            self._launch_predict_many(iw, R, Nn, D, T, max(lens),
-                                      return_beta)
-            out = iw["out"][:, :Nn].cpu()  # the chunk's one D2H copy
-            beta = iw["beta"][:Nn].cpu() if return_beta else None
-            for i, o, n in zip(idxs, offs, lens):
-                results[i] = self._pm_entry(out, beta, o, n, return_dist,
-                                            return_beta)
-        return results
+                    iw["eps"][:Nn].zero_()
+            else:
+                self._pm_pack_rows(iw["eps"], [eps[i] for i in idxs], offs,
+                                   lens)
+            if ys is not None:
+                if "label" not in iw:
+                    iw["label"] = torch.empty(iw["N"], device=self.device)
+                self._pm_pack_rows(iw["label"], [ys[i] for i in idxs], offs,
+                                   lens)
+            self._launch_predict_many(iw, R, Nn, D, T, max(lens), with_beta)
+            yield idxs, lens, offs, iw
+
+    @staticmethod
+    def _pm_pack_rows(dst, vals, offs, lens):
+        """Pack per-day (N_d,) vectors back to back into dst[:sum N_d]."""
+        Nn = offs[-1]
+        v = [t.reshape(-1).float() for t in vals]
+        if all(t.device.type == "cpu" for t in v):
+            dst[:Nn].copy_(torch.cat(v))
+        elif all(t.device == dst.device for t in v):
+            torch.cat(v, out=dst[:Nn])
+        else:
+            for t, o, n in zip(v, offs, lens):
+                dst[o:o + n].copy_(t)
 
     @staticmethod
     def _pm_entry(out, beta, o: int, n: int, return_dist: bool,
@@ -1731,6 +1768,97 @@ class FusedTrainer:
         if return_beta:
             entry.append(beta[o:o + n])
         return tuple(entry)
+
+    # ------------------------------------------------- on-device metrics
+    # longest day daily_ic_seg's LDS plan holds; longer days come back
+    # with count = -1
+    EVAL_MAX_N = 8192
+
+    @torch.no_grad()
+    def evaluate_many(self, days, on=("mu",), topk: int = 0, eps=None,
+                      max_rows: Optional[int] = None):
+        """Per-day IC, RankIC and top-k long/short returns of many trading
+        days, computed on the device from the batched scoring workspace.
+
+        days: list of (x_d (N_d, T, C), y_d (N_d, 1) or (N_d,)), host or
+        device. on: the prediction columns to rank on, a subset of
+        ("score", "mu") — the stochastic sample and the predictive mean.
+        eps as in predict_many; when None, "score" draws it and a
+        mu-only evaluation leaves torch's generator alone.
+
+        Days are packed and chunked exactly as in predict_many; after a
+        chunk's kernel sequence daily_ic_seg reads the requested rows of
+        the packed scores and only D*P*4 doubles + D*P ints come back to
+        the host. Returns {"columns": on, "ic", "rank_ic", "long",
+        "short": (D, P) float64, "count": (D, P) int32} as host tensors in
+        input-day order; definitions in factorvae_amd.metrics. Rows whose
+        prediction or label is not finite are left out and `count` is the
+        number of rows used; a day longer than 8192 stocks is reported as
+        count = -1 with NaN values. Like predict_many it touches no
+        training buffer, captured graph or in-graph RNG state."""
+        from ..metrics import check_columns
+
+        on = check_columns(on)
+        topk = int(topk)
+        if topk < 0:
+            raise ValueError(f"topk must be >= 0, got {topk}")
+        days = list(days)
+        xs = [x for x, _ in days]
+        ys = [y for _, y in days]
+        if eps is not None:
+            eps = list(eps)
+        D_all, P = len(days), len(on)
+        stats = torch.full((D_all, P, 4), float("nan"), dtype=torch.float64)
+        count = torch.zeros(D_all, P, dtype=torch.int32)
+        # rows of iw["out"]: sample, mu, sigma
+        row = {"score": 0, "mu": 1}
+        r_lo = min(row[c] for c in on)
+        r_hi = max(row[c] for c in on) + 1
+        col = [row[c] - r_lo for c in on]
+        Pk = r_hi - r_lo
+        for idxs, lens, offs, iw in self._pm_chunks(
+                "evaluate_many", xs, eps, max_rows, False, ys=ys,
+                draw_eps="score" in on):
+            if iw is None:
+                continue  # days without rows: count 0, NaN
+            D, Nn = len(idxs), offs[-1]
+            if iw.get("ic_cap", 0) < D * Pk:
+                iw["ic_stats"] = torch.empty(D * Pk * 4, device=self.device,
+                                             dtype=torch.float64)
+                iw["ic_count"] = torch.empty(D * Pk, device=self.device,
+                                             dtype=torch.int32)
+                iw["ic_cap"] = D * Pk
+            st, cn = iw["ic_stats"][:D * Pk * 4], iw["ic_count"][:D * Pk]
+            self.ext.daily_ic_seg(iw["out"][r_lo:r_hi, :Nn],
+                                  iw["label"][:Nn], iw["seg_off"][:D + 1],
+                                  min(max(lens), self.EVAL_MAX_N), topk, st,
+                                  cn)
+            st_h = st.cpu().view(D, Pk, 4)[:, col]
+            cn_h = cn.cpu().view(D, Pk)[:, col]
+            ii = torch.tensor(idxs)
+            stats[ii] = st_h
+            count[ii] = cn_h
+        return {"columns": on, "ic": stats[:, :, 0].clone(),
+                "rank_ic": stats[:, :, 1].clone(),
+                "long": stats[:, :, 2].clone(),
+                "short": stats[:, :, 3].clone(), "count": count}
+
+    @torch.no_grad()
+    def validate_metrics(self, days, topk: int = 0):
+        """Summary of evaluate_many on the predictive mean, dropout off:
+        {"IC", "ICIR", "RankIC", "RankIC_IR", "long_short", "n_days"}
+        (metrics.summarize_ic: means over the days with a finite value,
+        IR = mean / std with ddof=0)."""
+        from ..metrics import summarize_ic
+
+        was = self.training
+        self.training = False
+        try:
+            per_day = self.evaluate_many(days, on=("mu",), topk=topk)
+        finally:
+            self.training = was
+        return summarize_ic({k: per_day[k].numpy()
+                             for k in ("ic", "rank_ic", "long", "short")})
 
     # ------------------------------------------------------------- epochs
     # steps per multi-step training graph (real-epoch batching)

@@ -151,6 +151,13 @@ def train_main(args, data_args, df=None) -> float:
     loaders, flat-bucket gradient all-reduce, val-loss all-reduce,
     rank-0-only checkpointing. Returns best validation loss.
 
+    Opt-in ranking metrics: args.val_metrics computes the validation
+    range's daily IC / RankIC summary on the predictive mean after every
+    epoch (on the device with the fused engine, metrics.py's oracle with
+    the eager one) and logs it; args.select_by = "rankic" (implies
+    val_metrics) keeps the checkpoint of the best validation RankIC
+    instead of the lowest validation loss.
+
     Engines (args.engine, default "auto" = fused on GPU, eager on CPU):
     - "fused": the MI355X production path — device-resident epoch cache
       (one H2D per day ever), hipGraph-captured HIP-kernel step, fused
@@ -203,6 +210,18 @@ def train_main(args, data_args, df=None) -> float:
                                 args.num_portfolio, args.seed)
     sidecar = save_root + ".opt"
     resume = bool(getattr(args, "resume", False))
+    select_by = getattr(args, "select_by", None)
+    if (select_by is None and resume and os.path.exists(save_root)
+            and os.path.exists(sidecar)):
+        # a resumed run goes on selecting the way the side-car's run did
+        select_by = torch.load(sidecar, map_location="cpu",
+                               weights_only=True).get("select_by")
+    select_by = select_by or "loss"
+    if select_by not in ("loss", "rankic"):
+        raise ValueError(f"select_by must be loss or rankic, got {select_by}")
+    val_metrics = (bool(getattr(args, "val_metrics", False))
+                   or select_by == "rankic")
+    val_topk = int(getattr(args, "val_topk", 0) or 0)
 
     if engine == "fused":
         from ..data.device_cache import DeviceEpochCache
@@ -243,6 +262,15 @@ def train_main(args, data_args, df=None) -> float:
             select_feature=data_args.select_feature,
             rank=rank, world_size=world_size, seed=args.seed,
         )
+        if val_metrics:
+            # the full validation range on every rank: no communication,
+            # no wrap-pad duplicates
+            metric_days = [_split_batch(cwl, device) for cwl, _ in
+                           init_data_loader(
+                               df, shuffle=False, step_len=data_args.seq_len,
+                               start=data_args.val_start_time,
+                               end=data_args.val_end_time,
+                               select_feature=data_args.select_feature)]
         T_max = len(train_dataloader) * args.num_epochs
         factorVAE.to(device)
         grad_bucket = (FlatGradBucket(factorVAE.parameters())
@@ -253,12 +281,14 @@ def train_main(args, data_args, df=None) -> float:
 
     start_epoch = 0
     best_val_loss = float("inf")
+    best_val_rankic = float("-inf")
     if resume and os.path.exists(save_root) and os.path.exists(sidecar):
         state = torch.load(save_root, map_location=device, weights_only=True)
         factorVAE.load_state_dict(state)
         side = torch.load(sidecar, map_location="cpu", weights_only=True)
         start_epoch = int(side.get("epoch", 0))
         best_val_loss = float(side.get("best_val_loss", float("inf")))
+        best_val_rankic = float(side.get("best_val_rankic", float("-inf")))
         if trainer is not None and "fused_opt" in side:
             trainer.load_opt_state_dict(side["fused_opt"])
         elif optimizer is not None and "optimizer" in side:
@@ -296,13 +326,45 @@ def train_main(args, data_args, df=None) -> float:
             print(f"Epoch {epoch + 1}: Train Loss: {train_loss:.4f}, "
                   f"Validation Loss: {val_loss:.4f}, "
                   f"{rate_total:.1f} cross-sections/s")
-        logger.log({"Train Loss": train_loss, "Validation Loss": val_loss,
-                    "cross_sections_per_sec": rate_total}, step=epoch)
-        if val_loss < best_val_loss:
-            best_val_loss = val_loss
+        record = {"Train Loss": train_loss, "Validation Loss": val_loss,
+                  "cross_sections_per_sec": rate_total}
+        rankic = float("nan")
+        if val_metrics:
+            if engine == "fused":
+                vm = trainer.validate_metrics(valid_cache.days, topk=val_topk)
+            else:
+                from ..metrics import evaluate_days_eager, summarize_ic
+                vm = summarize_ic(evaluate_days_eager(
+                    factorVAE, metric_days, on=("mu",), topk=val_topk))
+            rankic = vm["RankIC"]
+            if rank == 0:
+                print(f"Epoch {epoch + 1}: Validation IC: {vm['IC']:.4f}, "
+                      f"Validation RankIC: {rankic:.4f}, "
+                      f"Validation RankIC_IR: {vm['RankIC_IR']:.4f}")
+            record.update({"Validation IC": vm["IC"],
+                           "Validation RankIC": rankic,
+                           "Validation RankIC_IR": vm["RankIC_IR"]})
+            if val_topk > 0:
+                record["Validation long_short"] = vm["long_short"]
+        logger.log(record, step=epoch)
+        if select_by == "rankic":
+            improved = rankic > best_val_rankic  # False for NaN
+            best_val_loss = min(best_val_loss, val_loss)
+            if improved:
+                best_val_rankic = rankic
+        else:
+            improved = val_loss < best_val_loss
+            if improved:
+                best_val_loss = val_loss
+            if val_metrics and rankic > best_val_rankic:
+                best_val_rankic = rankic
+        if improved:
             if rank == 0:
                 torch.save(factorVAE.state_dict(), save_root)
                 side = {"epoch": epoch + 1, "best_val_loss": best_val_loss}
+                if select_by == "rankic":
+                    side["select_by"] = select_by
+                    side["best_val_rankic"] = best_val_rankic
                 if trainer is not None:
                     side["fused_opt"] = trainer.opt_state_dict()
                 else:
@@ -311,5 +373,10 @@ def train_main(args, data_args, df=None) -> float:
                 torch.save(side, sidecar)
                 print(f"Model saved at {save_root}")
 
-    logger.finish({"Best Validation Loss": best_val_loss})
+    summary = {"Best Validation Loss": best_val_loss}
+    if val_metrics:
+        summary["Best Validation RankIC"] = (
+            best_val_rankic if best_val_rankic > float("-inf")
+            else float("nan"))
+    logger.finish(summary)
     return best_val_loss

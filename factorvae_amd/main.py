@@ -50,6 +50,19 @@ def build_argparser() -> argparse.ArgumentParser:
     parser.add_argument("--resume", action="store_true",
                         help="resume from the checkpoint + optimizer "
                              "side-car in save_dir if present")
+    parser.add_argument("--val_metrics", action="store_true",
+                        help="after each epoch also compute and log the "
+                             "validation range's daily IC / RankIC / "
+                             "RankIC_IR on the predictive mean")
+    parser.add_argument("--val_topk", type=int, default=0,
+                        help="with --val_metrics: k > 0 also logs the mean "
+                             "top-k minus bottom-k label spread")
+    parser.add_argument("--select_by", type=str, default=None,
+                        choices=["loss", "rankic"],
+                        help="checkpoint selection: lowest validation loss "
+                             "(default), or highest validation RankIC "
+                             "(implies --val_metrics); with --resume the "
+                             "default is what the resumed run used")
     return parser
 
 

@@ -212,6 +212,10 @@ hipError_t fv_dec_seg_fwd(const float*, const int*, const float*,
                           const float*, const float*, const float*,
                           const float*, float*, float*, float*, float*, int,
                           int, int, int, hipStream_t);
+// per-day ranking metrics of the packed scores (metrics.hip)
+hipError_t fv_daily_ic_seg(const float*, long, const float*, const int*,
+                           double*, int*, int, int, int, int, int,
+                           hipStream_t);
 hipError_t fv_step_inc(int*, hipStream_t);
 hipError_t fv_adam(float*, const float*, float*, float*, const int*, long,
                    float, float, float, float, float, float, hipStream_t);
@@ -1224,6 +1228,44 @@ void dec_seg_fwd(torch::Tensor h, torch::Tensor seg_off, torch::Tensor W1,
                      (int)D, (int)K, (int)H, cur_stream()));
 }
 
+// pred (P,total) fp32 rows with any row stride (a row slice of the scoring
+// workspace's (3,Nn) output), label (>= total) fp32, seg_off int32 (D+1);
+// max_n the longest day (sizes the launch's LDS, <= 8192). Outputs, fully
+// written: stats (D,P,4) float64 = ic, rank_ic, long, short; count (D,P)
+// int32 = valid rows, -1 for a refused segment.
+void daily_ic_seg(torch::Tensor pred, torch::Tensor label,
+                  torch::Tensor seg_off, long max_n, long topk,
+                  torch::Tensor stats, torch::Tensor count) {
+  TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == torch::kFloat32,
+              "pred must be fp32 on GPU");
+  TORCH_CHECK(pred.dim() == 2, "pred must be (P, total)");
+  const long P = pred.size(0), total = pred.size(1);
+  TORCH_CHECK(P >= 1, "pred needs at least one row");
+  TORCH_CHECK(total <= 1 || pred.stride(1) == 1,
+              "pred rows must be contiguous");
+  TORCH_CHECK(P == 1 || pred.stride(0) >= 0);
+  CK(label);
+  check_i32(seg_off, "seg_off");
+  check_i32(count, "count");
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() &&
+              stats.scalar_type() == torch::kFloat64,
+              "stats must be contiguous float64 on GPU");
+  const long D = seg_off.numel() - 1;
+  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
+  TORCH_CHECK(label.numel() >= total, "label shorter than the packed rows");
+  TORCH_CHECK(total < (1L << 31), "too many packed rows");
+  TORCH_CHECK(stats.numel() >= D * P * 4 && count.numel() >= D * P,
+              "per-day outputs too small");
+  TORCH_CHECK(max_n >= 0 && max_n <= 8192,
+              "daily_ic_seg supports days of up to 8192 rows, got max_n=",
+              max_n);
+  TORCH_CHECK(topk >= 0 && topk < (1L << 31), "topk out of range");
+  RUN(fv_daily_ic_seg(fp(pred), P > 1 ? (long)pred.stride(0) : 0L, fp(label),
+                      seg_off.data_ptr<int>(), stats.data_ptr<double>(),
+                      count.data_ptr<int>(), (int)total, (int)D, (int)P,
+                      (int)max_n, (int)topk, cur_stream()));
+}
+
 void dec_bwd(torch::Tensor drecon, torch::Tensor h, torch::Tensor a1,
              torch::Tensor beta, torch::Tensor asig_pre, torch::Tensor sigma,
              torch::Tensor eps, torch::Tensor fmu, torch::Tensor fsig_c,
@@ -1568,6 +1610,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("Wb"), py::arg("bb"), py::arg("fmu"), py::arg("fsig_c"),
           py::arg("eps"), py::arg("mu"), py::arg("sigma"),
           py::arg("sample") = py::none(), py::arg("beta") = py::none());
+  mod.def("daily_ic_seg", &daily_ic_seg,
+          py::arg("pred"), py::arg("label"), py::arg("seg_off"),
+          py::arg("max_n"), py::arg("topk"), py::arg("stats"),
+          py::arg("count"));
   mod.def("loss_fwd", &loss_fwd);
   mod.def("loss_bwd", &loss_bwd);
   mod.def("step_inc", &step_inc);

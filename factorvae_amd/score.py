@@ -14,6 +14,7 @@ Run:  python -m factorvae_amd.score --checkpoint best_models/x.pt \
 from __future__ import annotations
 
 import argparse
+import json
 import os
 
 import pandas as pd
@@ -61,9 +62,43 @@ def build_argparser() -> argparse.ArgumentParser:
                    help="with --backtest: also write backtest.png and the "
                         "plotly HTML report (the reference notebook's "
                         "backtest.png / backtest_plotly/ artifacts)")
+    p.add_argument("--metrics", action="store_true",
+                   help="also evaluate the range's daily IC / RankIC and "
+                        "top-k long/short spread on the predictive mean and "
+                        "write them as JSON next to the score CSV")
+    p.add_argument("--metrics_topk", type=int, default=50,
+                   help="k of the --metrics long/short spread")
     p.add_argument("--topk", type=int, default=50)
     p.add_argument("--n_drop", type=int, default=10)
     return p
+
+
+def range_metrics(model, loader, seq_length: int, engine: str = "auto",
+                  topk: int = 50):
+    """Summary of the loader's days ranked on the predictive mean: the
+    fused engine's on-device evaluation on a GPU (engine "auto"/"fused"),
+    metrics.py's oracle on the eager module otherwise."""
+    from .metrics import evaluate_days_eager, summarize_ic
+
+    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    model.to(device)
+    days = []
+    for char_with_label, _ in loader:
+        if char_with_label.shape[1] != seq_length:
+            continue
+        days.append((char_with_label[:, :, :-1].float(),
+                     char_with_label[:, -1, -1].float()))
+    from .engine.trainer import resolve_engine
+
+    hidden = model.feature_extractor.gru.hidden_size
+    if resolve_engine(engine, hidden, device.type, warn=False) == "fused":
+        from .engine.fused import FusedTrainer
+
+        trainer = FusedTrainer(model, lr=0.0, t_max=1, device=device,
+                               train=False)
+        return trainer.validate_metrics(days, topk=topk)
+    return summarize_ic(evaluate_days_eager(model, days, on=("mu",),
+                                            topk=topk))
 
 
 def main(argv=None):
@@ -94,6 +129,18 @@ def main(argv=None):
     out_csv = os.path.join(args.out_dir, fname)
     scores.to_csv(out_csv)
     print(f"wrote {out_csv}: {len(scores)} rows")
+
+    if args.metrics:
+        summary = range_metrics(model, loader, args.seq_length,
+                                engine=args.engine, topk=args.metrics_topk)
+        print("\nmetrics on mu:")
+        for k in ("IC", "ICIR", "RankIC", "RankIC_IR", "long_short",
+                  "n_days"):
+            print(f"  {k}: {summary[k]}")
+        out_json = os.path.splitext(out_csv)[0] + "_metrics.json"
+        with open(out_json, "w") as f:
+            json.dump(dict(summary, topk=args.metrics_topk), f, indent=1)
+        print(f"wrote {out_json}")
 
     if args.backtest:
         merged = scores.join(df[["LABEL0"]], how="inner")

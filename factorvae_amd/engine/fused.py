@@ -420,21 +420,14 @@ class FusedTrainer:
         # concurrently with the dec/enc wgrads that use tn_part_s
         w["tn_part_a"] = f(small_mn)
         # deterministic shared-grad partials (no float atomics anywhere)
-        dec_iters = min(8, max(1, (N + 511) // 512))
-        dec_nblk = (N + 4 * dec_iters - 1) // (4 * dec_iters) + 1
-        w["dec_part"] = f(dec_nblk * (2 * K + 2 * H + 2))
+        # (one block of slack beyond the decoder's own block count)
+        w["dec_part"] = f((self.ext.dec_nblk(N) + 1) * (2 * K + 2 * H + 2))
         w["hpart"] = f(K * (2 * H + 2))
-        cb = (C + 63) // 64
-        ty = (2048 + cb - 1) // cb
-        # mirror the launcher's rpb clamp to [64, 8192]
-        # (extractor.hip fv_ln_bwd_params): without the upper clamp,
-        # yblocks at very large R exceeds the partial buffer
-        rpb = min(8192, max(64, (R + ty - 1) // ty))
         w["dzx"] = f(R, C)
         if self._f32_tail != 2:
             # FV_F32_TAIL=2 never forms dxln (its LayerNorm gradients
             # come out of ln_w1x_finish)
-            w["ln_part"] = f(((R + rpb - 1) // rpb + 1) * 2 * C)
+            w["ln_part"] = f((self.ext.ln_bwd_yblocks(R, C) + 1) * 2 * C)
             w["dxln"] = f(R, C)
         if self.bf16:
             fb = lambda *shape: torch.zeros(*shape, device=d,
@@ -453,7 +446,7 @@ class FusedTrainer:
             if self._whh_fused:
                 # the in-GRU Whh wgrad replaces the dgh_bf operand image
                 # + h_prev cast with per-block partials
-                nblk = (N + 15) // 16
+                nblk = self.ext.gru_wgrad_blocks(N)
                 w["whh_part"] = f(nblk * 3 * H * H)
                 w["bhh_part"] = f(nblk * 3 * H)
             else:
@@ -798,8 +791,8 @@ class FusedTrainer:
         # workgroup sums the decoder's factor partials and adds the KL
         # gradients itself
         main.wait_event(e_att)
-        nblk = (N + 3) // 4
-        ext.enc_bwd_mid(w["dec_part"], nblk, w["fmu"], w["fsig_c"], w["pmu"],
+        ext.enc_bwd_mid(w["dec_part"], ext.dec_nblk(N), w["fmu"],
+                        w["fsig_c"], w["pmu"],
                         w["psig_c"], w["fsig"], w["fsig_pre"], w["yp"],
                         p("Wmu_e"), p("Wsig_e"), w["a_enc"], yv,
                         w["dscores"], g("Wmu_e"), g("bmu_e"), g("Wsig_e"),
@@ -936,7 +929,7 @@ class FusedTrainer:
                 if self._whh_fused:
                     ext.wgrad_reduce(w["whh_part"], g("Whh"),
                                      w["bhh_part"], g("bhh"),
-                                     (N + 15) // 16, False)
+                                     ext.gru_wgrad_blocks(N), False)
                 else:
                     ext.gemm_tn_bf16(w["dgh_bf"].view(R, 3 * H),
                                      w["h_prev_bf"], g("Whh"), w["tn_part"],

@@ -8,6 +8,7 @@
 // Adam update matches torch.optim.Adam defaults (bias-corrected).
 
 #include "common.h"
+#include "launchers.h"
 
 __global__ void step_inc_kernel(int* __restrict__ step_t) {
   if (threadIdx.x == 0 && blockIdx.x == 0) step_t[0] += 1;

@@ -10,6 +10,7 @@
 // This removes the reference's 2K serialized (N,H)x(H,H) GEMMs per step.
 
 #include "common.h"
+#include "launchers.h"
 #include "stage.h"
 
 // qk[k][i] = sum_j q[k][j] * Wk[k][j][i];  c[k] = sum_j q[k][j]*bk[k][j]

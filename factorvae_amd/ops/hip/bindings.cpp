@@ -1,251 +1,106 @@
 // Torch extension bindings for the FactorVAE gfx950 kernels.
 // Thin layer: validate tensors, extract raw pointers, forward to the
-// extern "C" launchers defined in the .hip translation units.
+// extern "C" launchers declared in launchers.h.
 
 #include <torch/extension.h>
 // Direct ATen/hip include (torch-ROCm's native header; no CUDA-named
 // compatibility path — the hipify build pass is a no-op on this file).
 #include <ATen/hip/HIPContext.h>
 
-#include <hip/hip_runtime_api.h>
+#include <climits>
 
-extern "C" {
-hipError_t fv_gemm_nt(const float*, const float*, const float*, float*, int,
-                      int, int, float, int, int, hipStream_t);
-hipError_t fv_gemm_nn(const float*, const float*, const float*, float*, int,
-                      int, int, float, int, int, const float*, hipStream_t);
-hipError_t fv_gemm_tn_pair(const float*, const float*, float*, float*, float*,
-                           float*, int, const float*, const float*, float*,
-                           float*, float*, float*, int, int, int, int, int,
-                           hipStream_t);
-int fv_tn_xhat_slices(int);
-hipError_t fv_gemm_tn_xhat(const float*, const float*, const float*,
-                           const float*, float*, float*, int, int, int,
-                           hipStream_t);
-hipError_t fv_ln_w1x_finish(const float*, const float*, const float*,
-                            const float*, const float*, float*, float*,
-                            float*, float*, int, int, hipStream_t);
-hipError_t fv_gemm_tn(const float*, const float*, float*, float*, float*,
-                      float*, int, int, int, int, int, hipStream_t);
-hipError_t fv_colsum(const float*, float*, int, int, int, hipStream_t);
-hipError_t fv_gemm_nt_bf16(const void*, const void*, const float*, float*,
-                           void*, int, int, int, float, int, int,
-                           hipStream_t);
-hipError_t fv_gemm_nn_bf16(const void*, const void*, const float*, float*,
-                           void*, const void*, int, int, int, float, int,
-                           int, hipStream_t);
-hipError_t fv_gemm_nt_bf16_rs(const void*, const void*, const float*,
-                              float*, void*, const void*, int, int, int,
-                              int, float, int, hipStream_t);
-hipError_t fv_cast_shadows(const float*, void*, void*, int, int, int, int,
-                           const float*, void*, void*, int, int, int, int,
-                           const float*, void*, long, hipStream_t);
-hipError_t fv_gemm_tn_bf16(const void*, const void*, float*, float*, float*,
-                           float*, int, int, int, int, int, hipStream_t);
-hipError_t fv_cast_f32_bf16(const float*, void*, long, hipStream_t);
-hipError_t fv_cast3_f32_bf16(const float*, void*, long, const float*, void*,
-                             long, const float*, void*, long, hipStream_t);
-hipError_t fv_lrelu_bwd_bf16(const void*, const void*, void*, long,
-                             hipStream_t);
-hipError_t fv_lrelu_bwd(const float*, const float*, float*, long, hipStream_t);
-hipError_t fv_ln_fwd(const float*, const float*, const float*, float*, void*,
-                     void*, int, float*, float*, long, int, float,
-                     hipStream_t);
-hipError_t fv_extractor_head_fwd(const float*, const float*, const float*,
-                                 const float*, const float*, const float*,
-                                 const float*, float*, float*, float*, float*,
-                                 float*, long, int, int, float, int, int*,
-                                 hipStream_t);
-hipError_t fv_gemm_nt_fp8(const void*, const void*, const float*,
-                          const float*, float*, void*, void*, int, int, int,
-                          int, int, int, float, int, int, hipStream_t);
-hipError_t fv_absmax_scale(const float*, long, float*, float*, hipStream_t);
-hipError_t fv_gemm_nt_fp8_rs(const void*, const void*, const float*,
-                             const float*, const float*, const void*,
-                             const float*, float*, float*, void*, void*,
-                             int, int, int, int, int, float, int, int,
-                             hipStream_t);
-hipError_t fv_scale_from_amax2(float*, float*, float*, float*, float*,
-                               float*, hipStream_t);
-hipError_t fv_cast_f32_fp8_damax(const float*, void*, const float*, float*,
-                                 long, int, int, hipStream_t);
-hipError_t fv_cast_f32_fp8_scaled_t(const float*, void*, const float*, int,
-                                    int, int, hipStream_t);
-hipError_t fv_cast_f32_fp8_scaled(const float*, void*, const float*, long,
-                                  int, int, hipStream_t);
-hipError_t fv_ln_bwd_params(const float*, const float*, const float*,
-                            const float*, float*, float*, float*, long, int,
-                            int, hipStream_t);
-hipError_t fv_gru_fwd(const float*, const float*, const float*, float*, float*,
-                      float*, float*, int, int, int, hipStream_t);
-hipError_t fv_gru_bwd(const float*, const float*, const float*, const float*,
-                      float*, float*, void*, void*, int, int, int,
-                      hipStream_t);
-hipError_t fv_gru_fwd_mfma(const float*, const void*, const float*, float*,
-                           float*, float*, float*, int, int, int,
-                           hipStream_t);
-hipError_t fv_gru_bwd_mfma(const float*, const float*, const float*,
-                           const void*, float*, float*, void*, void*,
-                           void*, int, const float*, float*, float*,
-                           float*, int, int, int, hipStream_t);
-hipError_t fv_wgrad_reduce(const float*, float*, long, const float*,
-                           float*, long, int, int, hipStream_t);
-hipError_t fv_enc_softmax_fwd(const float*, const float*, float*, float*, int,
-                              int, hipStream_t);
-hipError_t fv_enc_fused_fwd(const float*, const float*, const float*,
-                            const float*, float*, float*, float*,
-                            const float*, const float*, const float*,
-                            const float*, float*, float*, float*, float*,
-                            int*, int, int, int, int, int, hipStream_t);
-hipError_t fv_enc_bwd_fused(const float*, const float*, const float*,
-                            const float*, const float*, const float*,
-                            const float*, const float*, const float*,
-                            float*, float*, float*, float*, float*, int,
-                            int, int, hipStream_t);
-hipError_t fv_enc_softmax_bwd(const float*, const float*, const float*, float*,
-                              int, int, hipStream_t);
-hipError_t fv_enc_heads_fwd(const float*, const float*, const float*,
-                            const float*, const float*, float*, float*, float*,
-                            float*, int, int, hipStream_t);
-hipError_t fv_enc_heads_bwd(const float*, const float*, const float*,
-                            const float*, const float*, const float*,
-                            const float*, float*, float*, float*, float*,
-                            float*, int, int, hipStream_t);
-hipError_t fv_attn_qk_fwd(const float*, const float*, const float*, float*,
-                          float*, int, int, hipStream_t);
-hipError_t fv_attn_fused_bwd(const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             const int*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             float*, float*, float*, float*, float*, float*,
-                             float*, float*, float*, float*, float*, float*,
-                             float*, float*, int, int, int, float, float,
-                             int, const float*, const float*, const float*,
-                             const float*, float, hipStream_t);
-// the training step's middle chain (docs/KERNELS.md)
-hipError_t fv_dec_fwd_bwd(const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, float*, float*, float*, float*,
-                          float*, float*, float*, float*, float*, float*, int,
-                          int, int, float, hipStream_t);
-hipError_t fv_dec_bwd_reduce_heads(const float*, float*, float*, float*,
-                                   float*, int, int, int, hipStream_t);
-hipError_t fv_enc_bwd_mid(const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*, float*,
-                          float*, float*, float*, float*, float*, float*, int,
-                          int, int, int, float, hipStream_t);
-hipError_t fv_loss_scalars(const float*, const float*, const float*,
-                           const float*, const float*, const float*, float*,
-                           float*, float*, int, int, hipStream_t);
-hipError_t fv_attn_fused_fwd(const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             const float*, const float*, const float*,
-                             float*, float*, int*, float*, float*, float*,
-                             float*, float*, float*, float*, int, int, int,
-                             float, float, int, hipStream_t);
-hipError_t fv_attn_softmax_fwd(const float*, const float*, float*, float*,
-                               int*, int, int, float, hipStream_t);
-hipError_t fv_attn_ctx_fwd(const float*, const float*, const float*,
-                           const int*, float*, int, int, hipStream_t);
-hipError_t fv_attn_head_bwd(const float*, const float*, const float*,
-                            const int*, float*, float*, float*, int, int,
-                            hipStream_t);
-hipError_t fv_attn_softmax_bwd(const float*, const float*, const float*,
-                               const float*, const int*, float*, float*, int,
-                               int, float, float, hipStream_t);
-hipError_t fv_attn_qk_bwd(const float*, const float*, const float*,
-                          const float*, const float*, float*, float*, float*,
-                          int, int, hipStream_t);
-hipError_t fv_pred_mlp_fwd(const float*, const float*, const float*,
-                           const float*, const float*, const float*,
-                           const float*, float*, float*, float*, float*,
-                           float*, int, int, hipStream_t);
-hipError_t fv_pred_mlp_bwd(const float*, const float*, const float*,
-                           const float*, const float*, const float*,
-                           const float*, float*, float*, float*, float*,
-                           float*, float*, int, int, hipStream_t);
-hipError_t fv_dec_fwd(const float*, const float*, const float*, const float*,
-                      const float*, const float*, const float*, const float*,
-                      const float*, const float*, const float*, const float*,
-                      float*, float*, float*, float*, float*, int, int, int,
-                      hipStream_t);
-hipError_t fv_dec_bwd(const float*, const float*, const float*, const float*,
-                      const float*, const float*, const float*, const float*,
-                      const float*, const float*, const float*, const float*,
-                      const float*, float*, float*, float*, float*, float*,
-                      float*, float*, float*, float*, float*, int, int, int,
-                      hipStream_t);
-hipError_t fv_loss_fwd(const float*, const float*, const float*, const float*,
-                       const float*, const float*, float*, float*, float*, int,
-                       int, hipStream_t);
-hipError_t fv_loss_bwd(const float*, const float*, const float*, const float*,
-                       const float*, const float*, float*, float*, float*,
-                       float*, float*, int, int, float, hipStream_t);
-hipError_t fv_loss_fused(const float*, const float*, const float*,
-                         const float*, const float*, const float*, float*,
-                         float*, float*, float*, float*, float*, float*,
-                         float*, int, int, float, hipStream_t);
-hipError_t fv_dh_combine(float*, const float*, const float*, const float*,
-                         const float*, const float*, const float*, int, int,
-                         int, int, hipStream_t);
-// batched multi-day scoring (predict.hip + the GRU inference entries)
-hipError_t fv_gru_fwd_infer(const float*, const float*, const float*, float*,
-                            int, int, int, hipStream_t);
-hipError_t fv_gru_fwd_mfma_infer(const float*, const void*, const float*,
-                                 float*, int, int, int, hipStream_t);
-hipError_t fv_attn_seg_fwd(const float*, const int*, const float*,
-                           const float*, const float*, const float*,
-                           const float*, const float*, const float*,
-                           const float*, const float*, const float*, float*,
-                           float*, int*, int, int, int, int, int, float,
-                           hipStream_t);
-hipError_t fv_dec_seg_fwd(const float*, const int*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, const float*, const float*,
-                          const float*, float*, float*, float*, float*, int,
-                          int, int, int, hipStream_t);
-// per-day ranking metrics of the packed scores (metrics.hip)
-hipError_t fv_daily_ic_seg(const float*, long, const float*, const int*,
-                           double*, int*, int, int, int, int, int,
-                           hipStream_t);
-hipError_t fv_step_inc(int*, hipStream_t);
-hipError_t fv_adam(float*, const float*, float*, float*, const int*, long,
-                   float, float, float, float, float, float, hipStream_t);
-}
+#include "launchers.h"
 
 namespace {
+
+using torch::Tensor;
+using OptTensor = c10::optional<torch::Tensor>;
 
 inline hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
 
-inline const float* fp(const torch::Tensor& t) { return t.data_ptr<float>(); }
-inline float* fpm(torch::Tensor& t) { return t.data_ptr<float>(); }
+// The argument checks of one binding call. Every pointer handed to a
+// launcher comes out of ptr(): the tensor is on the GPU, on the device of
+// the call's first tensor, of the expected dtype, contiguous, and holds
+// the element count the call's dimensions need. Host metadata only — the
+// bindings run under graph capture. The kernel limits (H <= 64, ...) stay
+// in the launchers.
+class Op {
+ public:
+  Op(const char* name, const Tensor& first, const char* first_arg)
+      : name_(name), dev_(first.device()) {
+    TORCH_CHECK(first.is_cuda(), name_, ": ", first_arg,
+                " must be on the GPU");
+  }
 
-void check_f32(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
-}
+  // exact = false: at least n elements (activations, workspaces, outputs);
+  // exact = true: exactly n (parameters)
+  template <typename T>
+  T* ptr(const Tensor& t, const char* arg, at::ScalarType st, int64_t n,
+         bool exact) const {
+    TORCH_CHECK(n >= 0, name_, ": ", arg, " would need ", n, " elements");
+    TORCH_CHECK(t.is_cuda(), name_, ": ", arg, " must be on the GPU");
+    TORCH_CHECK(t.device() == dev_, name_, ": ", arg, " is on ", t.device(),
+                ", the call's first tensor on ", dev_);
+    TORCH_CHECK(t.scalar_type() == st, name_, ": ", arg, " must be ", st,
+                ", got ", t.scalar_type());
+    TORCH_CHECK(t.is_contiguous(), name_, ": ", arg, " must be contiguous");
+    TORCH_CHECK(exact ? t.numel() == n : t.numel() >= n, name_, ": ", arg,
+                " has ", t.numel(), " elements, needs ",
+                exact ? "exactly " : "at least ", n);
+    return static_cast<T*>(t.data_ptr());
+  }
+  // an absent optional tensor is a null pointer
+  template <typename T>
+  T* ptr(const OptTensor& t, const char* arg, at::ScalarType st, int64_t n,
+         bool exact) const {
+    return t.has_value() ? ptr<T>(*t, arg, st, n, exact) : nullptr;
+  }
 
-#define CK(t) check_f32(t, #t)
+  // size i of t (i = -1: the last) as a value that fits the launchers' int
+  long dim(const Tensor& t, const char* arg, int64_t i) const {
+    TORCH_CHECK(t.dim() > (i < 0 ? 0 : i), name_, ": ", arg, " must have ",
+                (i < 0 ? 1 : i + 1), " or more dimensions, got ", t.dim());
+    return num(t.size(i), arg);
+  }
+  // a size or count from Python, range-checked before it becomes an int
+  long num(int64_t v, const char* what) const {
+    TORCH_CHECK(v >= 0 && v <= INT_MAX, name_, ": ", what, " = ", v,
+                " is outside the range of int");
+    return v;
+  }
+  // the count that two tensors give together
+  int64_t same_numel(const Tensor& a, const char* an, const Tensor& b,
+                     const char* bn) const {
+    TORCH_CHECK(a.numel() == b.numel(), name_, ": ", an, " and ", bn,
+                " differ in size: ", a.numel(), " and ", b.numel(),
+                " elements");
+    return a.numel();
+  }
+  template <typename... Msg>
+  void require(bool ok, const Msg&... msg) const {
+    TORCH_CHECK(ok, name_, ": ", msg...);
+  }
 
-inline void check_bf16(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
-}
-#define CKB(t) check_bf16(t, #t)
-inline void* bfp(torch::Tensor& t) { return t.data_ptr(); }
-inline const void* bfpc(const torch::Tensor& t) { return t.data_ptr(); }
+ private:
+  const char* name_;
+  c10::Device dev_;
+};
+
+// OP opens a binding; the other macros use its `op` and report the argument
+// under its own name. n counts elements; the _EQ forms want exactly n.
+#define OP(name, first) const Op op(name, first, #first)
+#define P_F32(t, n) op.ptr<float>(t, #t, torch::kFloat32, n, false)
+#define P_F32_EQ(t, n) op.ptr<float>(t, #t, torch::kFloat32, n, true)
+#define P_BF16(t, n) op.ptr<void>(t, #t, torch::kBFloat16, n, false)
+#define P_BF16_EQ(t, n) op.ptr<void>(t, #t, torch::kBFloat16, n, true)
+#define P_FP8(t, n) op.ptr<void>(t, #t, torch::kFloat8_e4m3fn, n, false)
+#define P_I32(t, n) op.ptr<int>(t, #t, torch::kInt32, n, false)
+#define P_F64(t, n) op.ptr<double>(t, #t, torch::kFloat64, n, false)
+#define DIM(t, i) op.dim(t, #t, i)
+#define NUM(v) op.num(v, #v)
+
 #define RUN(call)                                                      \
   do {                                                                 \
     hipError_t e_ = (call);                                            \
@@ -253,979 +108,918 @@ inline const void* bfpc(const torch::Tensor& t) { return t.data_ptr(); }
                 (int)e_, ")");                                         \
   } while (0)
 
-void gemm_nt(torch::Tensor A, torch::Tensor W,
-             c10::optional<torch::Tensor> bias, torch::Tensor out,
-             double alpha, bool accumulate, bool act_lrelu) {
-  CK(A); CK(W); CK(out);
-  const int R = A.size(0), Ci = A.size(1), Co = W.size(0);
-  TORCH_CHECK(W.size(1) == Ci && out.size(0) == R && out.size(1) == Co);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  RUN(fv_gemm_nt(fp(A), fp(W), b, fpm(out), R, Ci, Co, (float)alpha,
-                 accumulate, act_lrelu, cur_stream()));
+// ---------------------------------------------------------------- fp32
+void gemm_nt(Tensor A, Tensor W, OptTensor bias, Tensor out, double alpha,
+             bool accumulate, bool act_lrelu) {
+  OP("gemm_nt", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), Co = DIM(W, 0);
+  op.require(DIM(W, 1) == Ci && DIM(out, 0) == R && DIM(out, 1) == Co,
+             "want A (R,Ci), W (Co,Ci), out (R,Co)");
+  RUN(fv_gemm_nt(P_F32(A, R * Ci), P_F32(W, Co * Ci), P_F32(bias, Co),
+                 P_F32(out, R * Co), R, Ci, Co, (float)alpha, accumulate,
+                 act_lrelu, cur_stream()));
 }
 
-void gemm_nn(torch::Tensor A, torch::Tensor B,
-             c10::optional<torch::Tensor> bias, torch::Tensor out,
-             double alpha, bool accumulate, bool act_lrelu,
-             c10::optional<torch::Tensor> lrelu_bwd_of = c10::nullopt) {
-  CK(A); CK(B); CK(out);
-  const int R = A.size(0), Ci = A.size(1), Co = B.size(1);
-  TORCH_CHECK(B.size(0) == Ci && out.size(0) == R && out.size(1) == Co);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  // optional epilogue: out *= lrelu'(Y), Y the post-activation (R,Co)
-  const float* yp = nullptr;
-  if (lrelu_bwd_of.has_value()) {
-    CK(*lrelu_bwd_of);
-    TORCH_CHECK(lrelu_bwd_of->dim() == 2 && lrelu_bwd_of->size(0) == R &&
-                lrelu_bwd_of->size(1) == Co);
-    yp = fp(*lrelu_bwd_of);
-  }
-  RUN(fv_gemm_nn(fp(A), fp(B), b, fpm(out), R, Ci, Co, (float)alpha,
-                 accumulate, act_lrelu, yp, cur_stream()));
+// optional epilogue: out *= lrelu'(Y), Y = lrelu_bwd_of the post-activation
+// (R,Co)
+void gemm_nn(Tensor A, Tensor B, OptTensor bias, Tensor out, double alpha,
+             bool accumulate, bool act_lrelu,
+             OptTensor lrelu_bwd_of = c10::nullopt) {
+  OP("gemm_nn", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), Co = DIM(B, 1);
+  op.require(DIM(B, 0) == Ci && DIM(out, 0) == R && DIM(out, 1) == Co,
+             "want A (R,Ci), B (Ci,Co), out (R,Co)");
+  op.require(!lrelu_bwd_of.has_value() ||
+                 (lrelu_bwd_of->dim() == 2 && lrelu_bwd_of->size(0) == R &&
+                  lrelu_bwd_of->size(1) == Co),
+             "lrelu_bwd_of must be (R,Co)");
+  RUN(fv_gemm_nn(P_F32(A, R * Ci), P_F32(B, Ci * Co), P_F32(bias, Co),
+                 P_F32(out, R * Co), R, Ci, Co, (float)alpha, accumulate,
+                 act_lrelu, P_F32(lrelu_bwd_of, R * Co), cur_stream()));
 }
 
-// ---------------------------------------------------------------- bf16
-void gemm_nt_bf16(torch::Tensor A, torch::Tensor W,
-                  c10::optional<torch::Tensor> bias,
-                  c10::optional<torch::Tensor> out_f32,
-                  c10::optional<torch::Tensor> out_bf16,
-                  double alpha, bool accumulate, bool act_lrelu) {
-  CKB(A); CKB(W);
-  const int R = A.size(0), Ci = A.size(1), Co = W.size(0);
-  TORCH_CHECK(W.size(1) == Ci);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  float* of = nullptr; void* ob = nullptr;
-  if (out_f32.has_value()) {
-    CK(*out_f32);
-    TORCH_CHECK(out_f32->size(0) == R && out_f32->size(1) == Co);
-    of = fpm(*out_f32);
-  }
-  if (out_bf16.has_value()) {
-    CKB(*out_bf16);
-    TORCH_CHECK(out_bf16->size(0) == R && out_bf16->size(1) == Co);
-    ob = bfp(*out_bf16);
-  }
-  TORCH_CHECK(of || ob, "need at least one output");
-  RUN(fv_gemm_nt_bf16(bfpc(A), bfpc(W), b, of, ob, R, Ci, Co, (float)alpha,
-                      accumulate, act_lrelu, cur_stream()));
-}
-
-void gemm_nn_bf16(torch::Tensor A, torch::Tensor B,
-                  c10::optional<torch::Tensor> bias,
-                  c10::optional<torch::Tensor> out_f32,
-                  c10::optional<torch::Tensor> out_bf16,
-                  double alpha, bool accumulate, bool act_lrelu,
-                  c10::optional<torch::Tensor> lrelu_bwd_of = c10::nullopt) {
-  CKB(A); CKB(B);
-  const int R = A.size(0), Ci = A.size(1), Co = B.size(1);
-  TORCH_CHECK(B.size(0) == Ci);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  float* of = nullptr; void* ob = nullptr;
-  if (out_f32.has_value()) {
-    CK(*out_f32);
-    TORCH_CHECK(out_f32->size(0) == R && out_f32->size(1) == Co);
-    of = fpm(*out_f32);
-  }
-  if (out_bf16.has_value()) {
-    CKB(*out_bf16);
-    TORCH_CHECK(out_bf16->size(0) == R && out_bf16->size(1) == Co);
-    ob = bfp(*out_bf16);
-  }
-  TORCH_CHECK(of || ob, "need at least one output");
-  const void* yp = nullptr;
-  if (lrelu_bwd_of.has_value()) {
-    CKB(*lrelu_bwd_of);
-    TORCH_CHECK(lrelu_bwd_of->size(0) == R && lrelu_bwd_of->size(1) == Co);
-    yp = bfpc(*lrelu_bwd_of);
-  }
-  RUN(fv_gemm_nn_bf16(bfpc(A), bfpc(B), b, of, ob, yp, R, Ci, Co,
-                      (float)alpha, accumulate, act_lrelu, cur_stream()));
-}
-
-void gemm_tn_bf16(torch::Tensor A, torch::Tensor B, torch::Tensor out,
-                  c10::optional<torch::Tensor> part, long r_chunks,
-                  bool accumulate, c10::optional<torch::Tensor> db,
-                  c10::optional<torch::Tensor> db_part) {
-  CKB(A); CKB(B); CK(out);
-  const int R = A.size(0), M = A.size(1), N = B.size(1);
-  TORCH_CHECK(B.size(0) == R && out.size(0) == M && out.size(1) == N);
-  long zmax = (R + 511) / 512;
-  if (zmax > 128) zmax = 128;
-  if (zmax < 1 || r_chunks <= 1) zmax = 1;
-  float* pp = nullptr;
-  if (part.has_value()) {
-    CK(*part);
-    TORCH_CHECK(part->numel() >= zmax * M * N, "partials too small");
-    pp = fpm(*part);
-  }
-  float* dbp = nullptr; float* dbpp = nullptr;
-  if (db.has_value()) {
-    CK(*db);
-    TORCH_CHECK(db->numel() == M);
-    dbp = fpm(*db);
-    if (db_part.has_value()) { CK(*db_part); dbpp = fpm(*db_part); }
-  }
-  RUN(fv_gemm_tn_bf16(bfpc(A), bfpc(B), fpm(out), pp, dbp, dbpp, R, M, N,
-                      (int)r_chunks, accumulate, cur_stream()));
-}
-
-void gemm_nt_bf16_rs(torch::Tensor A, torch::Tensor Wp,
-                     c10::optional<torch::Tensor> bias,
-                     c10::optional<torch::Tensor> out_f32,
-                     c10::optional<torch::Tensor> out_bf16,
-                     c10::optional<torch::Tensor> lrelu_bwd_of,
-                     double alpha, bool act_lrelu) {
-  CKB(A); CKB(Wp);
-  const int R = A.size(0), Ci = A.size(1), KP = Wp.size(1);
-  TORCH_CHECK(KP == ((Ci + 31) / 32) * 32, "Wp must be k-padded to 32");
-  int Co = -1;
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); Co = bias->numel(); }
-  float* of = nullptr; void* ob = nullptr;
-  if (out_f32.has_value()) {
-    CK(*out_f32);
-    Co = out_f32->size(1);
-    TORCH_CHECK(out_f32->size(0) == R);
-    of = fpm(*out_f32);
-  }
-  if (out_bf16.has_value()) {
-    CKB(*out_bf16);
-    Co = out_bf16->size(1);
-    TORCH_CHECK(out_bf16->size(0) == R);
-    ob = bfp(*out_bf16);
-  }
-  TORCH_CHECK(of || ob, "need at least one output");
-  TORCH_CHECK(Wp.size(0) >= Co, "Wp rows < Co");
-  const void* yp = nullptr;
-  if (lrelu_bwd_of.has_value()) {
-    CKB(*lrelu_bwd_of);
-    TORCH_CHECK(lrelu_bwd_of->size(0) == R && lrelu_bwd_of->size(1) == Co);
-    yp = bfpc(*lrelu_bwd_of);
-  }
-  RUN(fv_gemm_nt_bf16_rs(bfpc(A), bfpc(Wp), b, of, ob, yp, R, Ci, Co, KP,
-                         (float)alpha, act_lrelu, cur_stream()));
-}
-
-void cast_shadows(torch::Tensor s1, torch::Tensor d1, torch::Tensor d1t,
-                  torch::Tensor s2, torch::Tensor d2, torch::Tensor d2t,
-                  torch::Tensor s3, torch::Tensor d3) {
-  CK(s1); CKB(d1); CKB(d1t); CK(s2); CKB(d2); CKB(d2t); CK(s3); CKB(d3);
-  const int M1 = s1.size(0), N1 = s1.size(1);
-  const int M2 = s2.size(0), N2 = s2.size(1);
-  TORCH_CHECK(d1.size(0) == M1 && d1t.size(0) == N1);
-  TORCH_CHECK(d2.size(0) == M2 && d2t.size(0) == N2);
-  RUN(fv_cast_shadows(fp(s1), bfp(d1), bfp(d1t), M1, N1, (int)d1.size(1),
-                      (int)d1t.size(1), fp(s2), bfp(d2), bfp(d2t), M2, N2,
-                      (int)d2.size(1), (int)d2t.size(1), fp(s3), bfp(d3),
-                      s3.numel(), cur_stream()));
-}
-
-void cast3_f32_bf16(torch::Tensor s0, torch::Tensor d0, torch::Tensor s1,
-                    torch::Tensor d1, torch::Tensor s2, torch::Tensor d2) {
-  CK(s0); CKB(d0); CK(s1); CKB(d1); CK(s2); CKB(d2);
-  RUN(fv_cast3_f32_bf16(fp(s0), bfp(d0), s0.numel(), fp(s1), bfp(d1),
-                        s1.numel(), fp(s2), bfp(d2), s2.numel(),
-                        cur_stream()));
-}
-
-void cast_f32_bf16(torch::Tensor src, torch::Tensor dst) {
-  CK(src); CKB(dst);
-  TORCH_CHECK(src.numel() == dst.numel());
-  RUN(fv_cast_f32_bf16(fp(src), bfp(dst), src.numel(), cur_stream()));
-}
-
-void lrelu_bwd_bf16(torch::Tensor dY, torch::Tensor Y, torch::Tensor dZ) {
-  CKB(dY); CKB(Y); CKB(dZ);
-  RUN(fv_lrelu_bwd_bf16(bfpc(dY), bfpc(Y), bfp(dZ), dY.numel(),
-                        cur_stream()));
-}
-
-void gemm_tn(torch::Tensor A, torch::Tensor B, torch::Tensor out,
-             c10::optional<torch::Tensor> part, long r_chunks,
-             bool accumulate, c10::optional<torch::Tensor> db,
-             c10::optional<torch::Tensor> db_part) {
-  CK(A); CK(B); CK(out);
-  const int R = A.size(0), M = A.size(1), N = B.size(1);
-  TORCH_CHECK(B.size(0) == R && out.size(0) == M && out.size(1) == N);
-  float* pp = nullptr;
-  if (part.has_value()) {
-    CK(*part);
-    TORCH_CHECK(part->numel() >= (long)32 * M * N,
-                "tn partial workspace too small");
-    pp = fpm(*part);
-  }
-  float* dbp = nullptr;
-  float* dbpp = nullptr;
-  if (db.has_value()) {
-    CK(*db);
-    TORCH_CHECK(db->numel() == M, "db must be (M,)");
-    dbp = fpm(*db);
-    if (db_part.has_value()) {
-      CK(*db_part);
-      TORCH_CHECK(db_part->numel() >= (long)32 * M,
-                  "db partial workspace too small");
-      dbpp = fpm(*db_part);
-    }
-  }
-  RUN(fv_gemm_tn(fp(A), fp(B), fpm(out), pp, dbp, dbpp, R, M, N,
-                 (int)r_chunks, accumulate, cur_stream()));
+void gemm_tn(Tensor A, Tensor B, Tensor out, OptTensor part, long r_chunks,
+             bool accumulate, OptTensor db, OptTensor db_part) {
+  OP("gemm_tn", A);
+  const long R = DIM(A, 0), M = DIM(A, 1), N = DIM(B, 1);
+  op.require(DIM(B, 0) == R && DIM(out, 0) == M && DIM(out, 1) == N,
+             "want A (R,M), B (R,N), out (M,N)");
+  // the launcher splits R into at most 32 slices
+  float* dbp = P_F32_EQ(db, M);
+  float* dbpp = dbp ? P_F32(db_part, 32 * M) : nullptr;
+  RUN(fv_gemm_tn(P_F32(A, R * M), P_F32(B, R * N), P_F32(out, M * N),
+                 P_F32(part, 32 * M * N), dbp, dbpp, R, M, N, NUM(r_chunks),
+                 accumulate, cur_stream()));
 }
 
 // Two weight gradients over a common R and M in one launch (+ one
 // reduce): bit-identical to two gemm_tn calls with the same arguments.
-void gemm_tn_pair(torch::Tensor A0, torch::Tensor B0, torch::Tensor out0,
-                  torch::Tensor A1, torch::Tensor B1, torch::Tensor out1,
-                  c10::optional<torch::Tensor> part0,
-                  c10::optional<torch::Tensor> part1, long r_chunks,
-                  bool accumulate, c10::optional<torch::Tensor> db0,
-                  c10::optional<torch::Tensor> db1,
-                  c10::optional<torch::Tensor> db_part0,
-                  c10::optional<torch::Tensor> db_part1) {
-  CK(A0); CK(B0); CK(out0); CK(A1); CK(B1); CK(out1);
-  const int R = A0.size(0), M = A0.size(1);
-  const int N0 = B0.size(1), N1 = B1.size(1);
-  TORCH_CHECK(A1.size(0) == R && A1.size(1) == M && B0.size(0) == R &&
-              B1.size(0) == R, "pair needs a common R and M");
-  TORCH_CHECK(out0.size(0) == M && out0.size(1) == N0 &&
-              out1.size(0) == M && out1.size(1) == N1);
-  TORCH_CHECK(part0.has_value() == part1.has_value() &&
-              db0.has_value() == db1.has_value() &&
-              db_part0.has_value() == db_part1.has_value(),
-              "pair arguments come in twos");
-  float *pp0 = nullptr, *pp1 = nullptr;
-  if (part0.has_value()) {
-    CK(*part0); CK(*part1);
-    TORCH_CHECK(part0->numel() >= (long)32 * M * N0 &&
-                part1->numel() >= (long)32 * M * N1,
-                "tn partial workspace too small");
-    TORCH_CHECK(part0->data_ptr() != part1->data_ptr(),
-                "pair needs two distinct partial workspaces");
-    pp0 = fpm(*part0); pp1 = fpm(*part1);
-  }
-  float *dbp0 = nullptr, *dbp1 = nullptr, *dbpp0 = nullptr, *dbpp1 = nullptr;
-  if (db0.has_value()) {
-    CK(*db0); CK(*db1);
-    TORCH_CHECK(db0->numel() == M && db1->numel() == M, "db must be (M,)");
-    dbp0 = fpm(*db0); dbp1 = fpm(*db1);
-    if (db_part0.has_value()) {
-      CK(*db_part0); CK(*db_part1);
-      TORCH_CHECK(db_part0->numel() >= (long)32 * M &&
-                  db_part1->numel() >= (long)32 * M,
-                  "db partial workspace too small");
-      TORCH_CHECK(db_part0->data_ptr() != db_part1->data_ptr(),
-                  "pair needs two distinct db partial workspaces");
-      dbpp0 = fpm(*db_part0); dbpp1 = fpm(*db_part1);
-    }
-  }
-  RUN(fv_gemm_tn_pair(fp(A0), fp(B0), fpm(out0), pp0, dbp0, dbpp0, N0,
-                      fp(A1), fp(B1), fpm(out1), pp1, dbp1, dbpp1, N1, R, M,
-                      (int)r_chunks, accumulate, cur_stream()));
+void gemm_tn_pair(Tensor A0, Tensor B0, Tensor out0, Tensor A1, Tensor B1,
+                  Tensor out1, OptTensor part0, OptTensor part1,
+                  long r_chunks, bool accumulate, OptTensor db0,
+                  OptTensor db1, OptTensor db_part0, OptTensor db_part1) {
+  OP("gemm_tn_pair", A0);
+  const long R = DIM(A0, 0), M = DIM(A0, 1);
+  const long N0 = DIM(B0, 1), N1 = DIM(B1, 1);
+  op.require(DIM(A1, 0) == R && DIM(A1, 1) == M && DIM(B0, 0) == R &&
+                 DIM(B1, 0) == R, "pair needs a common R and M");
+  op.require(DIM(out0, 0) == M && DIM(out0, 1) == N0 && DIM(out1, 0) == M &&
+                 DIM(out1, 1) == N1, "want out0 (M,N0), out1 (M,N1)");
+  op.require(part0.has_value() == part1.has_value() &&
+                 db0.has_value() == db1.has_value() &&
+                 db_part0.has_value() == db_part1.has_value(),
+             "pair arguments come in twos");
+  float* pp0 = P_F32(part0, 32 * M * N0);
+  float* pp1 = P_F32(part1, 32 * M * N1);
+  op.require(!pp0 || pp0 != pp1, "pair needs two distinct partial workspaces");
+  float* dbp0 = P_F32_EQ(db0, M);
+  float* dbp1 = P_F32_EQ(db1, M);
+  float* dbpp0 = dbp0 ? P_F32(db_part0, 32 * M) : nullptr;
+  float* dbpp1 = dbp0 ? P_F32(db_part1, 32 * M) : nullptr;
+  op.require(!dbpp0 || dbpp0 != dbpp1,
+             "pair needs two distinct db partial workspaces");
+  RUN(fv_gemm_tn_pair(P_F32(A0, R * M), P_F32(B0, R * N0),
+                      P_F32(out0, M * N0), pp0, dbp0, dbpp0, N0,
+                      P_F32(A1, R * M), P_F32(B1, R * N1),
+                      P_F32(out1, M * N1), pp1, dbp1, dbpp1, N1, R, M,
+                      NUM(r_chunks), accumulate, cur_stream()));
 }
 
 // part[z](M,N) = A[slice z]^T @ ((x - mean) * rstd)[slice z],
 // db_part[z](M) = colsum(A[slice z]); returns the slice count z.
-long gemm_tn_xhat(torch::Tensor A, torch::Tensor x, torch::Tensor mean,
-                  torch::Tensor rstd, torch::Tensor part,
-                  torch::Tensor db_part) {
-  CK(A); CK(x); CK(mean); CK(rstd); CK(part); CK(db_part);
-  const int R = A.size(0), M = A.size(1), N = x.size(1);
-  TORCH_CHECK(x.size(0) == R && mean.numel() == R && rstd.numel() == R);
-  const int nz = fv_tn_xhat_slices(R);
-  TORCH_CHECK(part.numel() >= (long)nz * M * N,
-              "tn partial workspace too small");
-  TORCH_CHECK(db_part.numel() >= (long)nz * M,
-              "db partial workspace too small");
-  RUN(fv_gemm_tn_xhat(fp(A), fp(x), fp(mean), fp(rstd), fpm(part),
-                      fpm(db_part), R, M, N, cur_stream()));
+long gemm_tn_xhat(Tensor A, Tensor x, Tensor mean, Tensor rstd, Tensor part,
+                  Tensor db_part) {
+  OP("gemm_tn_xhat", A);
+  const long R = DIM(A, 0), M = DIM(A, 1), N = DIM(x, 1);
+  op.require(DIM(x, 0) == R, "want A (R,M), x (R,N)");
+  const long nz = fv_tn_xhat_slices(R);
+  RUN(fv_gemm_tn_xhat(P_F32(A, R * M), P_F32(x, R * N), P_F32_EQ(mean, R),
+                      P_F32_EQ(rstd, R), P_F32(part, nz * M * N),
+                      P_F32(db_part, nz * M), R, M, N, cur_stream()));
   return nz;
 }
 
 // LayerNorm + W1x parameter gradients from gemm_tn_xhat's slices
-void ln_w1x_finish(torch::Tensor part, torch::Tensor db_part, long nz,
-                   torch::Tensor W1x, torch::Tensor gamma, torch::Tensor beta,
-                   torch::Tensor gW1x, torch::Tensor gb1x,
-                   torch::Tensor dgamma, torch::Tensor dbeta) {
-  CK(part); CK(db_part); CK(W1x); CK(gamma); CK(beta); CK(gW1x); CK(gb1x);
-  CK(dgamma); CK(dbeta);
-  const int C = W1x.size(0);
-  TORCH_CHECK(W1x.dim() == 2 && W1x.size(1) == C && gW1x.numel() == (long)C * C);
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && gb1x.numel() == C &&
-              dgamma.numel() == C && dbeta.numel() == C);
-  TORCH_CHECK(nz >= 1 && nz <= 32 && part.numel() >= nz * (long)C * C &&
-              db_part.numel() >= nz * (long)C, "slice workspace too small");
-  RUN(fv_ln_w1x_finish(fp(part), fp(db_part), fp(W1x), fp(gamma), fp(beta),
-                       fpm(gW1x), fpm(gb1x), fpm(dgamma), fpm(dbeta), C,
-                       (int)nz, cur_stream()));
+void ln_w1x_finish(Tensor part, Tensor db_part, long nz, Tensor W1x,
+                   Tensor gamma, Tensor beta, Tensor gW1x, Tensor gb1x,
+                   Tensor dgamma, Tensor dbeta) {
+  OP("ln_w1x_finish", part);
+  const long C = DIM(W1x, 0);
+  op.require(W1x.dim() == 2 && W1x.size(1) == C, "W1x must be (C,C)");
+  op.require(nz >= 1 && nz <= 32, "nz = ", nz, " is outside 1..32");
+  RUN(fv_ln_w1x_finish(P_F32(part, nz * C * C), P_F32(db_part, nz * C),
+                       P_F32_EQ(W1x, C * C), P_F32_EQ(gamma, C),
+                       P_F32_EQ(beta, C), P_F32_EQ(gW1x, C * C),
+                       P_F32_EQ(gb1x, C), P_F32_EQ(dgamma, C),
+                       P_F32_EQ(dbeta, C), C, nz, cur_stream()));
 }
 
-void colsum(torch::Tensor A, torch::Tensor out, long r_chunks) {
-  CK(A); CK(out);
-  const int R = A.size(0), C = A.size(1);
-  TORCH_CHECK(out.numel() == C);
-  RUN(fv_colsum(fp(A), fpm(out), R, C, (int)r_chunks, cur_stream()));
+void colsum(Tensor A, Tensor out, long r_chunks) {
+  OP("colsum", A);
+  const long R = DIM(A, 0), C = DIM(A, 1);
+  RUN(fv_colsum(P_F32(A, R * C), P_F32_EQ(out, C), R, C, NUM(r_chunks),
+                cur_stream()));
 }
 
-void lrelu_bwd(torch::Tensor dY, torch::Tensor Y, torch::Tensor dZ) {
-  CK(dY); CK(Y); CK(dZ);
-  RUN(fv_lrelu_bwd(fp(dY), fp(Y), fpm(dZ), dY.numel(), cur_stream()));
+void lrelu_bwd(Tensor dY, Tensor Y, Tensor dZ) {
+  OP("lrelu_bwd", dY);
+  const int64_t n = dY.numel();
+  RUN(fv_lrelu_bwd(P_F32(dY, n), P_F32(Y, n), P_F32(dZ, n), n, cur_stream()));
 }
 
-void ln_fwd(torch::Tensor x, torch::Tensor gamma, torch::Tensor beta,
-            c10::optional<torch::Tensor> xln,
-            torch::Tensor mean, torch::Tensor rstd,
-            double eps, c10::optional<torch::Tensor> xln_bf = c10::nullopt,
-            c10::optional<torch::Tensor> xln_f8 = c10::nullopt) {
-  CK(x); CK(gamma); CK(beta); CK(mean); CK(rstd);
-  const long R = x.numel() / x.size(-1);
-  const int C = x.size(-1);
-  float* xo = nullptr;
-  if (xln.has_value()) { CK(*xln); xo = fpm(*xln); }
-  void* xb = nullptr;
-  if (xln_bf.has_value()) { CKB(*xln_bf); xb = bfp(*xln_bf); }
-  void* x8 = nullptr;
-  int f8_ld = 0;
-  if (xln_f8.has_value()) {
-    TORCH_CHECK(xln_f8->is_cuda() && xln_f8->is_contiguous());
-    TORCH_CHECK(xln_f8->scalar_type() == torch::kFloat8_e4m3fn);
-    x8 = xln_f8->data_ptr();
-    f8_ld = xln_f8->size(-1);
-  }
-  TORCH_CHECK(xo || xb || x8, "ln_fwd needs an output");
-  RUN(fv_ln_fwd(fp(x), fp(gamma), fp(beta), xo, xb, x8, f8_ld, fpm(mean),
-                fpm(rstd), R, C, (float)eps, cur_stream()));
+// ---------------------------------------------------------------- bf16
+void gemm_nt_bf16(Tensor A, Tensor W, OptTensor bias, OptTensor out_f32,
+                  OptTensor out_bf16, double alpha, bool accumulate,
+                  bool act_lrelu) {
+  OP("gemm_nt_bf16", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), Co = DIM(W, 0);
+  op.require(DIM(W, 1) == Ci, "want A (R,Ci), W (Co,Ci)");
+  float* of = P_F32_EQ(out_f32, R * Co);
+  void* ob = P_BF16_EQ(out_bf16, R * Co);
+  op.require(of || ob, "need at least one output");
+  RUN(fv_gemm_nt_bf16(P_BF16(A, R * Ci), P_BF16(W, Co * Ci), P_F32(bias, Co),
+                      of, ob, R, Ci, Co, (float)alpha, accumulate, act_lrelu,
+                      cur_stream()));
+}
+
+void gemm_nn_bf16(Tensor A, Tensor B, OptTensor bias, OptTensor out_f32,
+                  OptTensor out_bf16, double alpha, bool accumulate,
+                  bool act_lrelu, OptTensor lrelu_bwd_of = c10::nullopt) {
+  OP("gemm_nn_bf16", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), Co = DIM(B, 1);
+  op.require(DIM(B, 0) == Ci, "want A (R,Ci), B (Ci,Co)");
+  float* of = P_F32_EQ(out_f32, R * Co);
+  void* ob = P_BF16_EQ(out_bf16, R * Co);
+  op.require(of || ob, "need at least one output");
+  RUN(fv_gemm_nn_bf16(P_BF16(A, R * Ci), P_BF16(B, Ci * Co), P_F32(bias, Co),
+                      of, ob, P_BF16_EQ(lrelu_bwd_of, R * Co), R, Ci, Co,
+                      (float)alpha, accumulate, act_lrelu, cur_stream()));
+}
+
+void gemm_tn_bf16(Tensor A, Tensor B, Tensor out, OptTensor part,
+                  long r_chunks, bool accumulate, OptTensor db,
+                  OptTensor db_part) {
+  OP("gemm_tn_bf16", A);
+  const long R = DIM(A, 0), M = DIM(A, 1), N = DIM(B, 1);
+  op.require(DIM(B, 0) == R && DIM(out, 0) == M && DIM(out, 1) == N,
+             "want A (R,M), B (R,N), out (M,N)");
+  // the most slices the launcher can choose (its FV_TN_Z cap defaults to
+  // and never usefully exceeds 128)
+  long zmax = (R + 511) / 512;
+  if (zmax > 128) zmax = 128;
+  if (zmax < 1 || r_chunks <= 1) zmax = 1;
+  float* dbp = P_F32_EQ(db, M);
+  float* dbpp = dbp ? P_F32(db_part, zmax * M) : nullptr;
+  RUN(fv_gemm_tn_bf16(P_BF16(A, R * M), P_BF16(B, R * N), P_F32(out, M * N),
+                      P_F32(part, zmax * M * N), dbp, dbpp, R, M, N,
+                      NUM(r_chunks), accumulate, cur_stream()));
+}
+
+void gemm_nt_bf16_rs(Tensor A, Tensor Wp, OptTensor bias, OptTensor out_f32,
+                     OptTensor out_bf16, OptTensor lrelu_bwd_of, double alpha,
+                     bool act_lrelu) {
+  OP("gemm_nt_bf16_rs", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), KP = DIM(Wp, 1);
+  op.require(KP == ((Ci + 31) / 32) * 32, "Wp must be k-padded to 32");
+  // Co comes from whichever of bias / out_f32 / out_bf16 is given last
+  long Co = -1;
+  if (bias.has_value()) Co = NUM(bias->numel());
+  if (out_f32.has_value()) Co = DIM(*out_f32, 1);
+  if (out_bf16.has_value()) Co = DIM(*out_bf16, 1);
+  op.require(out_f32.has_value() || out_bf16.has_value(),
+             "need at least one output");
+  op.require(DIM(Wp, 0) >= Co, "Wp rows < Co");
+  RUN(fv_gemm_nt_bf16_rs(P_BF16(A, R * Ci), P_BF16(Wp, Co * KP),
+                         P_F32(bias, Co), P_F32_EQ(out_f32, R * Co),
+                         P_BF16_EQ(out_bf16, R * Co),
+                         P_BF16_EQ(lrelu_bwd_of, R * Co), R, Ci, Co, KP,
+                         (float)alpha, act_lrelu, cur_stream()));
+}
+
+// s1 (M1,N1) -> d1 (M1,KPn1) and its transpose d1t (N1,KPm1), the same for
+// s2, and s3 -> d3 elementwise
+void cast_shadows(Tensor s1, Tensor d1, Tensor d1t, Tensor s2, Tensor d2,
+                  Tensor d2t, Tensor s3, Tensor d3) {
+  OP("cast_shadows", s1);
+  const long M1 = DIM(s1, 0), N1 = DIM(s1, 1);
+  const long M2 = DIM(s2, 0), N2 = DIM(s2, 1);
+  op.require(DIM(d1, 0) == M1 && DIM(d1t, 0) == N1 && DIM(d2, 0) == M2 &&
+                 DIM(d2t, 0) == N2, "shadow rows do not match their source");
+  const long KPn1 = DIM(d1, 1), KPm1 = DIM(d1t, 1);
+  const long KPn2 = DIM(d2, 1), KPm2 = DIM(d2t, 1);
+  op.require(KPn1 >= N1 && KPm1 >= M1 && KPn2 >= N2 && KPm2 >= M2,
+             "shadow rows are shorter than their source");
+  const int64_t n3 = s3.numel();
+  RUN(fv_cast_shadows(P_F32(s1, M1 * N1), P_BF16(d1, M1 * KPn1),
+                      P_BF16(d1t, N1 * KPm1), M1, N1, KPn1, KPm1,
+                      P_F32(s2, M2 * N2), P_BF16(d2, M2 * KPn2),
+                      P_BF16(d2t, N2 * KPm2), M2, N2, KPn2, KPm2,
+                      P_F32(s3, n3), P_BF16(d3, n3), n3, cur_stream()));
+}
+
+void cast_f32_bf16(Tensor src, Tensor dst) {
+  OP("cast_f32_bf16", src);
+  const int64_t n = src.numel();
+  RUN(fv_cast_f32_bf16(P_F32(src, n), P_BF16_EQ(dst, n), n, cur_stream()));
+}
+
+void lrelu_bwd_bf16(Tensor dY, Tensor Y, Tensor dZ) {
+  OP("lrelu_bwd_bf16", dY);
+  const int64_t n = dY.numel();
+  RUN(fv_lrelu_bwd_bf16(P_BF16(dY, n), P_BF16(Y, n), P_BF16(dZ, n), n,
+                        cur_stream()));
+}
+
+// fixed-order sum of z per-block wgrad partials: out = sum part[z],
+// db = sum db_part[z]
+void wgrad_reduce(Tensor part, Tensor out, Tensor db_part, Tensor db, long z,
+                  bool accumulate) {
+  OP("wgrad_reduce", part);
+  const int64_t elems = out.numel(), m_elems = db.numel();
+  NUM(z);
+  RUN(fv_wgrad_reduce(P_F32(part, z * elems), P_F32(out, elems), elems,
+                      P_F32(db_part, z * m_elems), P_F32(db, m_elems),
+                      m_elems, z, accumulate, cur_stream()));
+}
+
+// ------------------------------------------------------------ extractor
+void ln_fwd(Tensor x, Tensor gamma, Tensor beta, OptTensor xln, Tensor mean,
+            Tensor rstd, double eps, OptTensor xln_bf = c10::nullopt,
+            OptTensor xln_f8 = c10::nullopt) {
+  OP("ln_fwd", x);
+  const long C = DIM(x, -1);
+  op.require(C >= 1, "x has no columns");
+  const int64_t R = x.numel() / C;
+  const long f8_ld = xln_f8.has_value() ? DIM(*xln_f8, -1) : 0;
+  op.require(!xln_f8.has_value() || f8_ld >= C, "xln_f8 rows shorter than C");
+  float* xo = P_F32(xln, R * C);
+  void* xb = P_BF16(xln_bf, R * C);
+  void* x8 = P_FP8(xln_f8, R * f8_ld);
+  op.require(xo || xb || x8, "needs an output");
+  RUN(fv_ln_fwd(P_F32(x, R * C), P_F32_EQ(gamma, C), P_F32_EQ(beta, C), xo,
+                xb, x8, f8_ld, P_F32(mean, R), P_F32(rstd, R), R, C,
+                (float)eps, cur_stream()));
 }
 
 // LayerNorm -> lrelu(xln @ W1x^T + b1x) -> xp @ Wih^T + bih in one launch,
 // bit-identical to ln_fwd + two gemm_nt calls. Returns false, launching
 // nothing, when the shape is outside the kernel's limits (extractor.hip).
-bool extractor_head_fwd(torch::Tensor x, torch::Tensor gamma,
-                        torch::Tensor beta, torch::Tensor W1x,
-                        torch::Tensor b1x, torch::Tensor Wih,
-                        torch::Tensor bih, c10::optional<torch::Tensor> xln,
-                        torch::Tensor mean, torch::Tensor rstd,
-                        torch::Tensor xp, torch::Tensor gi, double eps,
-                        int64_t strip) {
-  CK(x); CK(gamma); CK(beta); CK(W1x); CK(b1x); CK(Wih); CK(bih);
-  CK(mean); CK(rstd); CK(xp); CK(gi);
-  const int C = x.size(-1);
-  const long R = x.numel() / C;
-  const int G = Wih.size(0);
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && b1x.numel() == C);
-  TORCH_CHECK(W1x.dim() == 2 && W1x.size(0) == C && W1x.size(1) == C);
-  TORCH_CHECK(Wih.dim() == 2 && Wih.size(1) == C && bih.numel() == G);
-  TORCH_CHECK(mean.numel() == R && rstd.numel() == R);
-  TORCH_CHECK(xp.numel() == R * C && gi.numel() == R * (long)G);
-  float* xo = nullptr;
-  if (xln.has_value()) {
-    CK(*xln);
-    TORCH_CHECK(xln->numel() == R * C);
-    xo = fpm(*xln);
-  }
+bool extractor_head_fwd(Tensor x, Tensor gamma, Tensor beta, Tensor W1x,
+                        Tensor b1x, Tensor Wih, Tensor bih, OptTensor xln,
+                        Tensor mean, Tensor rstd, Tensor xp, Tensor gi,
+                        double eps, int64_t strip) {
+  OP("extractor_head_fwd", x);
+  const long C = DIM(x, -1), G = DIM(Wih, 0);
+  op.require(C >= 1, "x has no columns");
+  const int64_t R = x.numel() / C;
+  op.require(W1x.dim() == 2 && W1x.size(0) == C && W1x.size(1) == C,
+             "W1x must be (C,C)");
+  op.require(Wih.dim() == 2 && Wih.size(1) == C, "Wih must be (G,C)");
   int ran = 0;
-  RUN(fv_extractor_head_fwd(fp(x), fp(gamma), fp(beta), fp(W1x), fp(b1x),
-                            fp(Wih), fp(bih), xo, fpm(mean), fpm(rstd),
-                            fpm(xp), fpm(gi), R, C, G, (float)eps, (int)strip,
-                            &ran, cur_stream()));
+  RUN(fv_extractor_head_fwd(
+      P_F32(x, R * C), P_F32_EQ(gamma, C), P_F32_EQ(beta, C),
+      P_F32_EQ(W1x, C * C), P_F32_EQ(b1x, C), P_F32_EQ(Wih, G * C),
+      P_F32_EQ(bih, G), P_F32_EQ(xln, R * C), P_F32_EQ(mean, R),
+      P_F32_EQ(rstd, R), P_F32_EQ(xp, R * C), P_F32_EQ(gi, R * G), R, C, G,
+      (float)eps, NUM(strip), &ran, cur_stream()));
   return ran != 0;
 }
 
-inline void check_fp8(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == torch::kFloat8_e4m3fn, name,
-              " must be float8_e4m3fn");
+void ln_bwd_params(Tensor x, Tensor dxln, Tensor mean, Tensor rstd,
+                   Tensor part, Tensor dgamma, Tensor dbeta, long r_chunks) {
+  OP("ln_bwd_params", x);
+  const long C = DIM(x, -1);
+  op.require(C >= 1, "x has no columns");
+  const int64_t R = x.numel() / C;
+  const long yblocks = fv_ln_bwd_yblocks(R, C);
+  RUN(fv_ln_bwd_params(P_F32(x, R * C), P_F32(dxln, R * C), P_F32(mean, R),
+                       P_F32(rstd, R), P_F32(part, yblocks * 2 * C),
+                       P_F32_EQ(dgamma, C), P_F32_EQ(dbeta, C), R, C,
+                       NUM(r_chunks), cur_stream()));
 }
-#define CK8(t) check_fp8(t, #t)
 
+// ----------------------------------------------------------------- fp8
 // A/W fp8 (R, lda)/(Co, ldw) padded; logical K = Ci. Outputs optional.
-void gemm_nt_fp8(torch::Tensor A, torch::Tensor W,
-                 c10::optional<torch::Tensor> bias,
-                 c10::optional<torch::Tensor> inv_sw,
-                 c10::optional<torch::Tensor> out_f32,
-                 c10::optional<torch::Tensor> out_bf16,
-                 c10::optional<torch::Tensor> out_fp8,
+void gemm_nt_fp8(Tensor A, Tensor W, OptTensor bias, OptTensor inv_sw,
+                 OptTensor out_f32, OptTensor out_bf16, OptTensor out_fp8,
                  long R, long Ci, long Co, double alpha, bool act_lrelu) {
-  CK8(A); CK8(W);
-  const int lda = A.size(1), ldw = W.size(1);
-  TORCH_CHECK(A.size(0) >= R && lda >= Ci && W.size(0) >= Co && ldw >= Ci);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  const float* isw = nullptr;
-  if (inv_sw.has_value()) { CK(*inv_sw); isw = fp(*inv_sw); }
-  float* of = nullptr; void* ob = nullptr; void* o8 = nullptr; int ldo = 0;
-  if (out_f32.has_value()) { CK(*out_f32); of = fpm(*out_f32); }
-  if (out_bf16.has_value()) { CKB(*out_bf16); ob = bfp(*out_bf16); }
-  if (out_fp8.has_value()) {
-    CK8(*out_fp8);
-    o8 = out_fp8->data_ptr();
-    ldo = out_fp8->size(-1);
-  }
-  TORCH_CHECK(of || ob || o8, "need at least one output");
-  RUN(fv_gemm_nt_fp8(A.data_ptr(), W.data_ptr(), b, isw, of, ob, o8, ldo,
-                     (int)R, (int)Ci, (int)Co, lda, ldw, (float)alpha,
-                     act_lrelu, b != nullptr, cur_stream()));
+  OP("gemm_nt_fp8", A);
+  NUM(R); NUM(Ci); NUM(Co);
+  const long lda = DIM(A, 1), ldw = DIM(W, 1);
+  op.require(DIM(A, 0) >= R && lda >= Ci && DIM(W, 0) >= Co && ldw >= Ci,
+             "A / W smaller than R, Ci, Co");
+  const long ldo = out_fp8.has_value() ? DIM(*out_fp8, -1) : 0;
+  op.require(!out_fp8.has_value() || ldo >= Co, "out_fp8 rows shorter than Co");
+  const float* b = P_F32(bias, Co);
+  float* of = P_F32(out_f32, R * Co);
+  void* ob = P_BF16(out_bf16, R * Co);
+  void* o8 = P_FP8(out_fp8, R * ldo);
+  op.require(of || ob || o8, "need at least one output");
+  RUN(fv_gemm_nt_fp8(P_FP8(A, R * lda), P_FP8(W, Co * ldw), b,
+                     P_F32(inv_sw, 1), of, ob, o8, ldo, R, Ci, Co, lda, ldw,
+                     (float)alpha, act_lrelu, b != nullptr, cur_stream()));
 }
 
-void gemm_nt_fp8_rs(torch::Tensor A, torch::Tensor Wp,
-                    c10::optional<torch::Tensor> bias,
-                    c10::optional<torch::Tensor> inv_sw,
-                    c10::optional<torch::Tensor> out_f32,
-                    c10::optional<torch::Tensor> out_bf16,
-                    c10::optional<torch::Tensor> out_fp8,
+void gemm_nt_fp8_rs(Tensor A, Tensor Wp, OptTensor bias, OptTensor inv_sw,
+                    OptTensor out_f32, OptTensor out_bf16, OptTensor out_fp8,
                     long R, long Ci, long Co, double alpha, bool act_lrelu,
-                    c10::optional<torch::Tensor> inv_sa = c10::nullopt,
-                    c10::optional<torch::Tensor> lrelu_bwd_of = c10::nullopt,
-                    c10::optional<torch::Tensor> s_out = c10::nullopt,
-                    c10::optional<torch::Tensor> amax_out = c10::nullopt) {
-  CK8(A); CK8(Wp);
-  const int KP = A.size(1);
-  TORCH_CHECK(Wp.size(1) == KP && (KP & 127) == 0 && KP >= Ci,
-              "A/Wp must share a 128-padded k stride");
-  TORCH_CHECK(A.size(0) >= R && Wp.size(0) >= Co);
-  const float* b = nullptr;
-  if (bias.has_value()) { CK(*bias); b = fp(*bias); }
-  const float* isw = nullptr;
-  if (inv_sw.has_value()) { CK(*inv_sw); isw = fp(*inv_sw); }
-  const float* isa = nullptr;
-  if (inv_sa.has_value()) { CK(*inv_sa); isa = fp(*inv_sa); }
-  const void* yp = nullptr;
-  if (lrelu_bwd_of.has_value()) {
-    CKB(*lrelu_bwd_of);
-    yp = bfpc(*lrelu_bwd_of);
-  }
-  const float* sop = nullptr;
-  if (s_out.has_value()) { CK(*s_out); sop = fp(*s_out); }
-  float* amp = nullptr;
-  if (amax_out.has_value()) { CK(*amax_out); amp = fpm(*amax_out); }
-  float* of = nullptr; void* ob = nullptr; void* o8 = nullptr; int ldo = 0;
-  if (out_f32.has_value()) { CK(*out_f32); of = fpm(*out_f32); }
-  if (out_bf16.has_value()) { CKB(*out_bf16); ob = bfp(*out_bf16); }
-  if (out_fp8.has_value()) {
-    CK8(*out_fp8);
-    o8 = out_fp8->data_ptr();
-    ldo = out_fp8->size(-1);
-  }
-  TORCH_CHECK(of || ob || o8, "need at least one output");
-  RUN(fv_gemm_nt_fp8_rs(A.data_ptr(), Wp.data_ptr(), b, isw, isa, yp, sop,
-                        amp, of, ob, o8, ldo, (int)R, (int)Ci, (int)Co, KP,
-                        (float)alpha, act_lrelu, b != nullptr,
-                        cur_stream()));
+                    OptTensor inv_sa = c10::nullopt,
+                    OptTensor lrelu_bwd_of = c10::nullopt,
+                    OptTensor s_out = c10::nullopt,
+                    OptTensor amax_out = c10::nullopt) {
+  OP("gemm_nt_fp8_rs", A);
+  NUM(R); NUM(Ci); NUM(Co);
+  const long KP = DIM(A, 1);
+  op.require(DIM(Wp, 1) == KP && (KP & 127) == 0 && KP >= Ci,
+             "A/Wp must share a 128-padded k stride");
+  op.require(DIM(A, 0) >= R && DIM(Wp, 0) >= Co,
+             "A / Wp smaller than R, Co");
+  const long ldo = out_fp8.has_value() ? DIM(*out_fp8, -1) : 0;
+  op.require(!out_fp8.has_value() || ldo >= Co, "out_fp8 rows shorter than Co");
+  const float* b = P_F32(bias, Co);
+  float* of = P_F32(out_f32, R * Co);
+  void* ob = P_BF16(out_bf16, R * Co);
+  void* o8 = P_FP8(out_fp8, R * ldo);
+  op.require(of || ob || o8, "need at least one output");
+  RUN(fv_gemm_nt_fp8_rs(P_FP8(A, R * KP), P_FP8(Wp, Co * KP), b,
+                        P_F32(inv_sw, 1), P_F32(inv_sa, 1),
+                        P_BF16(lrelu_bwd_of, R * Co), P_F32(s_out, 1),
+                        P_F32(amax_out, 1), of, ob, o8, ldo, R, Ci, Co, KP,
+                        (float)alpha, act_lrelu, b != nullptr, cur_stream()));
 }
 
-void scale_from_amax2(torch::Tensor amax1, torch::Tensor s1,
-                      torch::Tensor is1, torch::Tensor amax2,
-                      torch::Tensor s2, torch::Tensor is2) {
-  CK(amax1); CK(s1); CK(is1); CK(amax2); CK(s2); CK(is2);
-  RUN(fv_scale_from_amax2(fpm(amax1), fpm(s1), fpm(is1), fpm(amax2),
-                          fpm(s2), fpm(is2), cur_stream()));
-}
-
-void cast_f32_fp8_damax(torch::Tensor src, torch::Tensor dst,
-                        torch::Tensor s, torch::Tensor amax_out) {
-  CK(src); CK8(dst); CK(s); CK(amax_out);
-  const long rows = src.numel() / src.size(-1);
-  const int cols = src.size(-1);
-  TORCH_CHECK(dst.size(-1) >= cols && dst.numel() / dst.size(-1) >= rows);
-  RUN(fv_cast_f32_fp8_damax(fp(src), dst.data_ptr(), fp(s), fpm(amax_out),
-                            rows, cols, (int)dst.size(-1), cur_stream()));
-}
-
-void cast_f32_fp8_scaled_t(torch::Tensor src, torch::Tensor dstT,
-                           torch::Tensor scale) {
-  CK(src); CK8(dstT); CK(scale);
-  const int M = src.size(0), N = src.size(1);
-  TORCH_CHECK(dstT.size(0) >= N && dstT.size(1) >= M);
-  RUN(fv_cast_f32_fp8_scaled_t(fp(src), dstT.data_ptr(), fp(scale), M, N,
-                               (int)dstT.size(1), cur_stream()));
-}
-
-void absmax_scale(torch::Tensor src, torch::Tensor scale,
-                  torch::Tensor inv_scale) {
-  CK(src); CK(scale); CK(inv_scale);
-  RUN(fv_absmax_scale(fp(src), src.numel(), fpm(scale), fpm(inv_scale),
-                      cur_stream()));
-}
-
-void cast_f32_fp8_scaled(torch::Tensor src, torch::Tensor dst,
-                         c10::optional<torch::Tensor> scale) {
-  CK(src); CK8(dst);
-  const long rows = src.numel() / src.size(-1);
-  const int cols = src.size(-1);
-  TORCH_CHECK(dst.size(-1) >= cols && dst.numel() / dst.size(-1) >= rows);
-  const float* sp = nullptr;
-  if (scale.has_value()) { CK(*scale); sp = fp(*scale); }
-  RUN(fv_cast_f32_fp8_scaled(fp(src), dst.data_ptr(), sp, rows, cols,
-                             (int)dst.size(-1), cur_stream()));
-}
-
-void ln_bwd_params(torch::Tensor x, torch::Tensor dxln, torch::Tensor mean,
-                   torch::Tensor rstd, torch::Tensor part,
-                   torch::Tensor dgamma, torch::Tensor dbeta, long r_chunks) {
-  CK(x); CK(dxln); CK(mean); CK(rstd); CK(part); CK(dgamma); CK(dbeta);
-  const long R = x.numel() / x.size(-1);
-  const int C = x.size(-1);
-  RUN(fv_ln_bwd_params(fp(x), fp(dxln), fp(mean), fp(rstd), fpm(part),
-                       fpm(dgamma), fpm(dbeta), R, C, (int)r_chunks,
-                       cur_stream()));
-}
-
-void gru_fwd(torch::Tensor gi, torch::Tensor Whh, torch::Tensor bhh,
-             torch::Tensor h_final, c10::optional<torch::Tensor> h_seq,
-             torch::Tensor h_prev, torch::Tensor gates4, long N, long T,
-             long H) {
-  CK(gi); CK(Whh); CK(bhh); CK(h_final); CK(h_prev); CK(gates4);
-  float* hs = nullptr;
-  if (h_seq.has_value()) { CK(*h_seq); hs = fpm(*h_seq); }
-  RUN(fv_gru_fwd(fp(gi), fp(Whh), fp(bhh), fpm(h_final), hs,
-                 fpm(h_prev), fpm(gates4), (int)N, (int)T, (int)H,
-                 cur_stream()));
-}
-
-void gru_bwd(torch::Tensor dh_final, torch::Tensor h_prev, torch::Tensor gates4,
-             torch::Tensor Whh, torch::Tensor dgi, torch::Tensor dgh, long N,
-             long T, long H,
-             c10::optional<torch::Tensor> dgi_bf = c10::nullopt,
-             c10::optional<torch::Tensor> dgh_bf = c10::nullopt) {
-  CK(dh_final); CK(h_prev); CK(gates4); CK(Whh); CK(dgi); CK(dgh);
-  void* gib = nullptr; void* ghb = nullptr;
-  if (dgi_bf.has_value()) { CKB(*dgi_bf); gib = bfp(*dgi_bf); }
-  if (dgh_bf.has_value()) { CKB(*dgh_bf); ghb = bfp(*dgh_bf); }
-  RUN(fv_gru_bwd(fp(dh_final), fp(h_prev), fp(gates4), fp(Whh), fpm(dgi),
-                 fpm(dgh), gib, ghb, (int)N, (int)T, (int)H, cur_stream()));
-}
-
-void gru_fwd_mfma(torch::Tensor gi, torch::Tensor whh_bf, torch::Tensor bhh,
-                  torch::Tensor h_final, c10::optional<torch::Tensor> h_seq,
-                  torch::Tensor h_prev, torch::Tensor gates4, long N, long T,
-                  long H) {
-  CK(gi); CKB(whh_bf); CK(bhh); CK(h_final); CK(h_prev);
-  CK(gates4);
-  float* hs = nullptr;
-  if (h_seq.has_value()) { CK(*h_seq); hs = fpm(*h_seq); }
-  RUN(fv_gru_fwd_mfma(fp(gi), bfpc(whh_bf), fp(bhh), fpm(h_final),
-                      hs, fpm(h_prev), fpm(gates4), (int)N, (int)T,
-                      (int)H, cur_stream()));
-}
-
-void gru_bwd_mfma(torch::Tensor dh_final, torch::Tensor h_prev,
-                  torch::Tensor gates4, torch::Tensor whh_bf,
-                  c10::optional<torch::Tensor> dgi,
-                  c10::optional<torch::Tensor> dgh, long N, long T,
-                  long H,
-                  c10::optional<torch::Tensor> dgi_bf = c10::nullopt,
-                  c10::optional<torch::Tensor> dgh_bf = c10::nullopt,
-                  c10::optional<torch::Tensor> dgi_f8 = c10::nullopt,
-                  c10::optional<torch::Tensor> s_dgi = c10::nullopt,
-                  c10::optional<torch::Tensor> amax_dgi = c10::nullopt,
-                  c10::optional<torch::Tensor> whh_part = c10::nullopt,
-                  c10::optional<torch::Tensor> bhh_part = c10::nullopt) {
-  CK(dh_final); CK(h_prev); CK(gates4); CKB(whh_bf);
-  float* gi = nullptr; float* gh = nullptr;
-  if (dgi.has_value()) { CK(*dgi); gi = fpm(*dgi); }
-  if (dgh.has_value()) { CK(*dgh); gh = fpm(*dgh); }
-  void* gib = nullptr; void* ghb = nullptr;
-  if (dgi_bf.has_value()) { CKB(*dgi_bf); gib = bfp(*dgi_bf); }
-  if (dgh_bf.has_value()) { CKB(*dgh_bf); ghb = bfp(*dgh_bf); }
-  void* g8 = nullptr; int ld8 = 0;
-  const float* sd = nullptr; float* am = nullptr;
-  if (dgi_f8.has_value()) {
-    CK8(*dgi_f8);
-    g8 = dgi_f8->data_ptr();
-    ld8 = dgi_f8->size(-1);
-    TORCH_CHECK(s_dgi.has_value() && amax_dgi.has_value(),
-                "dgi_f8 needs s_dgi + amax_dgi");
-    CK(*s_dgi); CK(*amax_dgi);
-    sd = fp(*s_dgi);
-    am = fpm(*amax_dgi);
-  }
-  TORCH_CHECK(gi || gib || g8, "gru_bwd_mfma needs a dgi output");
-  float* wp = nullptr; float* bp = nullptr;
-  if (whh_part.has_value()) {
-    CK(*whh_part);
-    TORCH_CHECK(bhh_part.has_value(), "whh_part needs bhh_part");
-    CK(*bhh_part);
-    const long nblk = (N + 15) / 16;
-    TORCH_CHECK(whh_part->numel() >= nblk * 192 * 64 &&
-                bhh_part->numel() >= nblk * 192, "wgrad partials too small");
-    wp = fpm(*whh_part);
-    bp = fpm(*bhh_part);
-  }
-  RUN(fv_gru_bwd_mfma(fp(dh_final), fp(h_prev), fp(gates4), bfpc(whh_bf),
-                      gi, gh, gib, ghb, g8, ld8, sd, am, wp, bp, (int)N,
-                      (int)T, (int)H, cur_stream()));
-}
-
-void wgrad_reduce(torch::Tensor part, torch::Tensor out,
-                  torch::Tensor db_part, torch::Tensor db, long z,
-                  bool accumulate) {
-  CK(part); CK(out); CK(db_part); CK(db);
-  RUN(fv_wgrad_reduce(fp(part), fpm(out), out.numel(), fp(db_part),
-                      fpm(db), db.numel(), (int)z, accumulate,
-                      cur_stream()));
-}
-
-void attn_fused_fwd(torch::Tensor h, torch::Tensor qk, torch::Tensor cb,
-                    c10::optional<torch::Tensor> mask, torch::Tensor Wv,
-                    torch::Tensor bv, torch::Tensor Wl, torch::Tensor bl,
-                    torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
-                    torch::Tensor bsig, torch::Tensor a, torch::Tensor sd,
-                    torch::Tensor guard, torch::Tensor u, torch::Tensor ctx,
-                    torch::Tensor hm2, torch::Tensor pmu,
-                    torch::Tensor psig_pre, torch::Tensor psig,
-                    torch::Tensor psig_c, double alpha, double keep_inv,
-                    int variant) {
-  CK(h); CK(qk); CK(cb); CK(Wv); CK(bv); CK(Wl); CK(bl); CK(wmu); CK(bmu);
-  CK(wsig); CK(bsig); CK(a); CK(sd); CK(u); CK(ctx); CK(hm2); CK(pmu);
-  CK(psig_pre); CK(psig); CK(psig_c);
-  TORCH_CHECK(guard.scalar_type() == torch::kInt32);
-  const int N = h.size(0), H = h.size(1), K = qk.size(0);
-  const float* mp = nullptr;
-  if (mask.has_value()) { CK(*mask); mp = fp(*mask); }
-  RUN(fv_attn_fused_fwd(fp(h), fp(qk), fp(cb), mp, fp(Wv), fp(bv), fp(Wl),
-                        fp(bl), fp(wmu), fp(bmu), fp(wsig), fp(bsig),
-                        fpm(a), fpm(sd), guard.data_ptr<int>(), fpm(u),
-                        fpm(ctx), fpm(hm2), fpm(pmu), fpm(psig_pre),
-                        fpm(psig), fpm(psig_c), N, K, H, (float)alpha,
-                        (float)keep_inv, variant, cur_stream()));
-}
-
-void attn_fused_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c,
-                    torch::Tensor psig, torch::Tensor psig_pre,
-                    torch::Tensor hm2, torch::Tensor wmu, torch::Tensor wsig,
-                    torch::Tensor Wl, torch::Tensor h, torch::Tensor a,
-                    torch::Tensor sd, c10::optional<torch::Tensor> mask,
-                    torch::Tensor guard, torch::Tensor u, torch::Tensor Wv,
-                    torch::Tensor q, torch::Tensor Wk, torch::Tensor bk,
-                    torch::Tensor dz2, torch::Tensor du, torch::Tensor ds,
-                    torch::Tensor dc, torch::Tensor dWv, torch::Tensor dbv,
-                    torch::Tensor dq, torch::Tensor dWk, torch::Tensor dbk,
-                    torch::Tensor hpart,
-                    torch::Tensor dwmu, torch::Tensor dbmu,
-                    torch::Tensor dwsig, torch::Tensor dbsig,
-                    double alpha, double keep_inv, int variant,
-                    c10::optional<torch::Tensor> kl_fmu = c10::nullopt,
-                    c10::optional<torch::Tensor> kl_fsig_c = c10::nullopt,
-                    c10::optional<torch::Tensor> kl_pmu = c10::nullopt,
-                    c10::optional<torch::Tensor> kl_psig_c = c10::nullopt,
-                    double kl_gscale = 1.0) {
-  CK(h); CK(a); CK(sd); CK(u); CK(Wv); CK(q); CK(Wk); CK(bk); CK(dz2);
-  CK(du); CK(ds); CK(dc); CK(dWv); CK(dbv); CK(dq); CK(dWk); CK(dbk);
-  CK(hpart);
-  const int N = h.size(0), H = h.size(1), K = q.size(0);
-  TORCH_CHECK(hpart.numel() >= (long)K * (2 * H + 2));
-  const float* mp = nullptr;
-  if (mask.has_value()) { CK(*mask); mp = fp(*mask); }
-  // in-kernel KL gradients: all four inputs or none; dpmu and dpsig_c
-  // are then outputs
-  const float* kfm = nullptr; const float* kfs = nullptr;
-  const float* kpm = nullptr; const float* kps = nullptr;
-  if (kl_fmu.has_value()) {
-    TORCH_CHECK(kl_fsig_c.has_value() && kl_pmu.has_value() &&
-                kl_psig_c.has_value(), "kl_* come as a set of four");
-    CK(*kl_fmu); CK(*kl_fsig_c); CK(*kl_pmu); CK(*kl_psig_c);
-    CK(dpmu); CK(dpsig_c);
-    TORCH_CHECK(kl_fmu->numel() >= K && kl_fsig_c->numel() >= K &&
-                kl_pmu->numel() >= K && kl_psig_c->numel() >= K &&
-                dpmu.numel() >= K && dpsig_c.numel() >= K, "kl_* sizes");
-    kfm = fp(*kl_fmu); kfs = fp(*kl_fsig_c);
-    kpm = fp(*kl_pmu); kps = fp(*kl_psig_c);
-  }
-  RUN(fv_attn_fused_bwd(fp(dpmu), fp(dpsig_c), fp(psig), fp(psig_pre),
-                        fp(hm2), fp(wmu), fp(wsig), fp(Wl), fp(h), fp(a),
-                        fp(sd), mp, guard.data_ptr<int>(), fp(u), fp(Wv),
-                        fp(q), fp(Wk), fp(bk), fpm(dz2), fpm(du), fpm(ds),
-                        fpm(dc), fpm(dWv), fpm(dbv), fpm(dq), fpm(dWk),
-                        fpm(dbk), fpm(hpart), fpm(dwmu), fpm(dbmu),
-                        fpm(dwsig), fpm(dbsig), N, K, H, (float)alpha,
-                        (float)keep_inv, variant, kfm, kfs, kpm, kps,
-                        (float)kl_gscale, cur_stream()));
-}
-
-void enc_fused_fwd(torch::Tensor h, torch::Tensor Wenc, torch::Tensor benc,
-                   torch::Tensor y, torch::Tensor scores, torch::Tensor a,
-                   torch::Tensor yp,
-                   c10::optional<torch::Tensor> Wmu = c10::nullopt,
-                   c10::optional<torch::Tensor> bmu = c10::nullopt,
-                   c10::optional<torch::Tensor> Wsig = c10::nullopt,
-                   c10::optional<torch::Tensor> bsig = c10::nullopt,
-                   c10::optional<torch::Tensor> fmu = c10::nullopt,
-                   c10::optional<torch::Tensor> fsig_pre = c10::nullopt,
-                   c10::optional<torch::Tensor> fsig = c10::nullopt,
-                   c10::optional<torch::Tensor> fsig_c = c10::nullopt,
-                   c10::optional<torch::Tensor> done = c10::nullopt,
-                   int variant = 1) {
-  CK(h); CK(Wenc); CK(benc); CK(y); CK(scores); CK(a); CK(yp);
-  const int N = h.size(0), H = h.size(1), M = Wenc.size(0);
-  const float* wm = nullptr; const float* bm = nullptr;
-  const float* ws = nullptr; const float* bs = nullptr;
-  float* fm = nullptr; float* fsp = nullptr; float* fs = nullptr;
-  float* fsc = nullptr; int* dn = nullptr; int K = 0;
-  if (fmu.has_value()) {
-    CK(*Wmu); CK(*bmu); CK(*Wsig); CK(*bsig); CK(*fmu); CK(*fsig_pre);
-    CK(*fsig); CK(*fsig_c);
-    TORCH_CHECK(done.has_value() &&
-                done->scalar_type() == torch::kInt32 && done->is_cuda(),
-                "fused heads need an int32 done counter");
-    wm = fp(*Wmu); bm = fp(*bmu); ws = fp(*Wsig); bs = fp(*bsig);
-    fm = fpm(*fmu); fsp = fpm(*fsig_pre); fs = fpm(*fsig);
-    fsc = fpm(*fsig_c);
-    dn = done->data_ptr<int>();
-    K = fmu->numel();
-    TORCH_CHECK(Wmu->size(0) == K && Wmu->size(1) == M);
-  }
-  RUN(fv_enc_fused_fwd(fp(h), fp(Wenc), fp(benc), fp(y), fpm(scores),
-                       fpm(a), fpm(yp), wm, bm, ws, bs, fm, fsp, fs, fsc,
-                       dn, K, N, M, H, variant, cur_stream()));
-}
-
-void enc_bwd_fused(torch::Tensor dfmu, torch::Tensor dfsig_c,
-                   torch::Tensor fsig, torch::Tensor fsig_pre,
-                   torch::Tensor yp, torch::Tensor Wmu, torch::Tensor Wsig,
-                   torch::Tensor a, torch::Tensor y, torch::Tensor dscores,
-                   torch::Tensor dWmu, torch::Tensor dbmu,
-                   torch::Tensor dWsig, torch::Tensor dbsig) {
-  CK(dfmu); CK(fsig); CK(yp); CK(Wmu); CK(Wsig); CK(a); CK(y); CK(dscores);
-  CK(dWmu); CK(dbmu); CK(dWsig); CK(dbsig);
-  const int N = a.size(0), M = a.size(1), K = Wmu.size(0);
-  RUN(fv_enc_bwd_fused(fp(dfmu), fp(dfsig_c), fp(fsig), fp(fsig_pre),
-                       fp(yp), fp(Wmu), fp(Wsig), fp(a), fp(y),
-                       fpm(dscores), fpm(dWmu), fpm(dbmu), fpm(dWsig),
-                       fpm(dbsig), N, M, K, cur_stream()));
-}
-
-void enc_softmax_fwd(torch::Tensor scores, torch::Tensor y, torch::Tensor a,
-                     torch::Tensor yp) {
-  CK(scores); CK(y); CK(a); CK(yp);
-  RUN(fv_enc_softmax_fwd(fp(scores), fp(y), fpm(a), fpm(yp),
-                         scores.size(0), scores.size(1), cur_stream()));
-}
-
-void enc_softmax_bwd(torch::Tensor dyp, torch::Tensor a, torch::Tensor y,
-                     torch::Tensor dscores) {
-  CK(dyp); CK(a); CK(y); CK(dscores);
-  RUN(fv_enc_softmax_bwd(fp(dyp), fp(a), fp(y), fpm(dscores), a.size(0),
-                         a.size(1), cur_stream()));
-}
-
-void enc_heads_fwd(torch::Tensor yp, torch::Tensor Wmu, torch::Tensor bmu,
-                   torch::Tensor Wsig, torch::Tensor bsig, torch::Tensor fmu,
-                   torch::Tensor fsig_pre, torch::Tensor fsig,
-                   torch::Tensor fsig_c) {
-  CK(yp); CK(Wmu); CK(bmu); CK(Wsig); CK(bsig); CK(fmu); CK(fsig_pre);
-  CK(fsig); CK(fsig_c);
-  RUN(fv_enc_heads_fwd(fp(yp), fp(Wmu), fp(bmu), fp(Wsig), fp(bsig), fpm(fmu),
-                       fpm(fsig_pre), fpm(fsig), fpm(fsig_c), yp.numel(),
-                       Wmu.size(0), cur_stream()));
-}
-
-void enc_heads_bwd(torch::Tensor dfmu, torch::Tensor dfsig_c,
-                   torch::Tensor fsig, torch::Tensor fsig_pre,
-                   torch::Tensor yp, torch::Tensor Wmu, torch::Tensor Wsig,
-                   torch::Tensor dyp, torch::Tensor dWmu, torch::Tensor dbmu,
-                   torch::Tensor dWsig, torch::Tensor dbsig) {
-  CK(dfmu); CK(dfsig_c); CK(fsig); CK(fsig_pre); CK(yp); CK(Wmu); CK(Wsig);
-  CK(dyp); CK(dWmu); CK(dbmu); CK(dWsig); CK(dbsig);
-  RUN(fv_enc_heads_bwd(fp(dfmu), fp(dfsig_c), fp(fsig), fp(fsig_pre), fp(yp),
-                       fp(Wmu), fp(Wsig), fpm(dyp), fpm(dWmu), fpm(dbmu),
-                       fpm(dWsig), fpm(dbsig), yp.numel(), Wmu.size(0),
-                       cur_stream()));
-}
-
-void attn_qk_fwd(torch::Tensor q, torch::Tensor Wk, torch::Tensor bk,
-                 torch::Tensor qk, torch::Tensor c) {
-  CK(q); CK(Wk); CK(bk); CK(qk); CK(c);
-  RUN(fv_attn_qk_fwd(fp(q), fp(Wk), fp(bk), fpm(qk), fpm(c), q.size(0),
-                     q.size(1), cur_stream()));
-}
-
-void attn_softmax_fwd(torch::Tensor s, c10::optional<torch::Tensor> mask,
-                      torch::Tensor a, torch::Tensor sd, torch::Tensor guard,
-                      double keep_inv) {
-  CK(s); CK(a); CK(sd);
-  TORCH_CHECK(guard.scalar_type() == torch::kInt32 && guard.is_cuda());
-  const float* mp = nullptr;
-  if (mask.has_value()) { CK(*mask); mp = fp(*mask); }
-  RUN(fv_attn_softmax_fwd(fp(s), mp, fpm(a), fpm(sd), guard.data_ptr<int>(),
-                          s.size(0), s.size(1), (float)keep_inv,
+void scale_from_amax2(Tensor amax1, Tensor s1, Tensor is1, Tensor amax2,
+                      Tensor s2, Tensor is2) {
+  OP("scale_from_amax2", amax1);
+  RUN(fv_scale_from_amax2(P_F32(amax1, 1), P_F32(s1, 1), P_F32(is1, 1),
+                          P_F32(amax2, 1), P_F32(s2, 1), P_F32(is2, 1),
                           cur_stream()));
 }
 
-void attn_ctx_fwd(torch::Tensor u, torch::Tensor Wv, torch::Tensor bv,
-                  torch::Tensor guard, torch::Tensor ctx) {
-  CK(u); CK(Wv); CK(bv); CK(ctx);
-  RUN(fv_attn_ctx_fwd(fp(u), fp(Wv), fp(bv), guard.data_ptr<int>(), fpm(ctx),
-                      u.size(0), u.size(1), cur_stream()));
+void cast_f32_fp8_damax(Tensor src, Tensor dst, Tensor s, Tensor amax_out) {
+  OP("cast_f32_fp8_damax", src);
+  const long cols = DIM(src, -1), ldp = DIM(dst, -1);
+  op.require(cols >= 1 && ldp >= cols, "dst rows shorter than src's");
+  const int64_t rows = src.numel() / cols;
+  RUN(fv_cast_f32_fp8_damax(P_F32(src, rows * cols), P_FP8(dst, rows * ldp),
+                            P_F32(s, 1), P_F32(amax_out, 1), rows, cols, ldp,
+                            cur_stream()));
 }
 
-void attn_head_bwd(torch::Tensor dctx, torch::Tensor u, torch::Tensor Wv,
-                   torch::Tensor guard, torch::Tensor du, torch::Tensor dWv,
-                   torch::Tensor dbv) {
-  CK(dctx); CK(u); CK(Wv); CK(du); CK(dWv); CK(dbv);
-  RUN(fv_attn_head_bwd(fp(dctx), fp(u), fp(Wv), guard.data_ptr<int>(),
-                       fpm(du), fpm(dWv), fpm(dbv), u.size(0), u.size(1),
+void cast_f32_fp8_scaled_t(Tensor src, Tensor dstT, Tensor scale) {
+  OP("cast_f32_fp8_scaled_t", src);
+  const long M = DIM(src, 0), N = DIM(src, 1), ldp = DIM(dstT, 1);
+  op.require(DIM(dstT, 0) >= N && ldp >= M, "dstT smaller than (N,M)");
+  RUN(fv_cast_f32_fp8_scaled_t(P_F32(src, M * N), P_FP8(dstT, N * ldp),
+                               P_F32(scale, 1), M, N, ldp, cur_stream()));
+}
+
+void absmax_scale(Tensor src, Tensor scale, Tensor inv_scale) {
+  OP("absmax_scale", src);
+  const int64_t n = src.numel();
+  RUN(fv_absmax_scale(P_F32(src, n), n, P_F32(scale, 1),
+                      P_F32(inv_scale, 1), cur_stream()));
+}
+
+void cast_f32_fp8_scaled(Tensor src, Tensor dst, OptTensor scale) {
+  OP("cast_f32_fp8_scaled", src);
+  const long cols = DIM(src, -1), ldp = DIM(dst, -1);
+  op.require(cols >= 1 && ldp >= cols, "dst rows shorter than src's");
+  const int64_t rows = src.numel() / cols;
+  RUN(fv_cast_f32_fp8_scaled(P_F32(src, rows * cols), P_FP8(dst, rows * ldp),
+                             P_F32(scale, 1), rows, cols, ldp, cur_stream()));
+}
+
+// ----------------------------------------------------------------- GRU
+// gi (N,T,3H); h_final (N,H); h_seq / h_prev (N,T,H); gates4 (N,T,4H)
+void gru_fwd(Tensor gi, Tensor Whh, Tensor bhh, Tensor h_final,
+             OptTensor h_seq, Tensor h_prev, Tensor gates4, long N, long T,
+             long H) {
+  OP("gru_fwd", gi);
+  NUM(N); NUM(T); NUM(H);
+  RUN(fv_gru_fwd(P_F32(gi, N * T * 3 * H), P_F32_EQ(Whh, 3 * H * H),
+                 P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H),
+                 P_F32(h_seq, N * T * H), P_F32(h_prev, N * T * H),
+                 P_F32(gates4, N * T * 4 * H), N, T, H, cur_stream()));
+}
+
+void gru_bwd(Tensor dh_final, Tensor h_prev, Tensor gates4, Tensor Whh,
+             Tensor dgi, Tensor dgh, long N, long T, long H,
+             OptTensor dgi_bf = c10::nullopt,
+             OptTensor dgh_bf = c10::nullopt) {
+  OP("gru_bwd", dh_final);
+  NUM(N); NUM(T); NUM(H);
+  const long G = N * T * 3 * H;
+  RUN(fv_gru_bwd(P_F32(dh_final, N * H), P_F32(h_prev, N * T * H),
+                 P_F32(gates4, N * T * 4 * H), P_F32_EQ(Whh, 3 * H * H),
+                 P_F32(dgi, G), P_F32(dgh, G), P_BF16(dgi_bf, G),
+                 P_BF16(dgh_bf, G), N, T, H, cur_stream()));
+}
+
+void gru_fwd_mfma(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
+                  OptTensor h_seq, Tensor h_prev, Tensor gates4, long N,
+                  long T, long H) {
+  OP("gru_fwd_mfma", gi);
+  NUM(N); NUM(T); NUM(H);
+  RUN(fv_gru_fwd_mfma(P_F32(gi, N * T * 3 * H), P_BF16_EQ(whh_bf, 3 * H * H),
+                      P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H),
+                      P_F32(h_seq, N * T * H), P_F32(h_prev, N * T * H),
+                      P_F32(gates4, N * T * 4 * H), N, T, H, cur_stream()));
+}
+
+// dgi_f8 (N*T, ld8) e4m3 comes with s_dgi and amax_dgi; whh_part / bhh_part
+// take one (3H,H) / (3H) wgrad partial per workgroup
+void gru_bwd_mfma(Tensor dh_final, Tensor h_prev, Tensor gates4,
+                  Tensor whh_bf, OptTensor dgi, OptTensor dgh, long N, long T,
+                  long H, OptTensor dgi_bf = c10::nullopt,
+                  OptTensor dgh_bf = c10::nullopt,
+                  OptTensor dgi_f8 = c10::nullopt,
+                  OptTensor s_dgi = c10::nullopt,
+                  OptTensor amax_dgi = c10::nullopt,
+                  OptTensor whh_part = c10::nullopt,
+                  OptTensor bhh_part = c10::nullopt) {
+  OP("gru_bwd_mfma", dh_final);
+  NUM(N); NUM(T); NUM(H);
+  const long G = N * T * 3 * H;
+  const long ld8 = dgi_f8.has_value() ? DIM(*dgi_f8, -1) : 0;
+  op.require(!dgi_f8.has_value() || (ld8 >= 3 * H && s_dgi.has_value() &&
+                                     amax_dgi.has_value()),
+             "dgi_f8 needs rows of 3H or more, s_dgi and amax_dgi");
+  op.require(!whh_part.has_value() || bhh_part.has_value(),
+             "whh_part needs bhh_part");
+  const long nblk = fv_gru_wgrad_blocks(N);
+  float* gi = P_F32(dgi, G);
+  void* gib = P_BF16(dgi_bf, G);
+  void* g8 = P_FP8(dgi_f8, N * T * ld8);
+  op.require(gi || gib || g8, "needs a dgi output");
+  float* wp = P_F32(whh_part, nblk * 3 * H * H);
+  RUN(fv_gru_bwd_mfma(P_F32(dh_final, N * H), P_F32(h_prev, N * T * H),
+                      P_F32(gates4, N * T * 4 * H),
+                      P_BF16_EQ(whh_bf, 3 * H * H), gi, P_F32(dgh, G), gib,
+                      P_BF16(dgh_bf, G), g8, ld8,
+                      g8 ? P_F32(s_dgi, 1) : nullptr,
+                      g8 ? P_F32(amax_dgi, 1) : nullptr, wp,
+                      wp ? P_F32(bhh_part, nblk * 3 * H) : nullptr, N, T, H,
+                      cur_stream()));
+}
+
+// Inference forward: h_final only, no backward state
+void gru_fwd_infer(Tensor gi, Tensor Whh, Tensor bhh, Tensor h_final, long N,
+                   long T, long H) {
+  OP("gru_fwd_infer", gi);
+  NUM(N); NUM(T); NUM(H);
+  RUN(fv_gru_fwd_infer(P_F32(gi, N * T * 3 * H), P_F32_EQ(Whh, 3 * H * H),
+                       P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H), N, T, H,
                        cur_stream()));
 }
 
-void attn_softmax_bwd(torch::Tensor da, torch::Tensor a, torch::Tensor sd,
-                      c10::optional<torch::Tensor> mask, torch::Tensor guard,
-                      torch::Tensor ds, torch::Tensor dc, double keep_inv,
+void gru_fwd_mfma_infer(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
+                        long N, long T, long H) {
+  OP("gru_fwd_mfma_infer", gi);
+  NUM(N); NUM(T); NUM(H);
+  RUN(fv_gru_fwd_mfma_infer(P_F32(gi, N * T * 3 * H),
+                            P_BF16_EQ(whh_bf, 3 * H * H),
+                            P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H), N, T,
+                            H, cur_stream()));
+}
+
+// ------------------------------------------------------------ attention
+// h (N,H); qk (K,H); per-head weights Wv (K,H,H), bv (K,H); the predictor
+// MLP Wl (H,H), bl / wmu / wsig (H), bmu / bsig (1); a / sd / mask (N,K);
+// u / ctx / hm2 (K,H); guard int32 (K); pmu ... psig_c (K).
+// variant: 1 = latency-oriented kernel (default), 0 = original kernel
+void attn_fused_fwd(Tensor h, Tensor qk, Tensor cb, OptTensor mask, Tensor Wv,
+                    Tensor bv, Tensor Wl, Tensor bl, Tensor wmu, Tensor bmu,
+                    Tensor wsig, Tensor bsig, Tensor a, Tensor sd,
+                    Tensor guard, Tensor u, Tensor ctx, Tensor hm2,
+                    Tensor pmu, Tensor psig_pre, Tensor psig, Tensor psig_c,
+                    double alpha, double keep_inv, int variant) {
+  OP("attn_fused_fwd", h);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(qk, 0);
+  op.require(DIM(qk, 1) == H, "qk must be (K,H)");
+  RUN(fv_attn_fused_fwd(
+      P_F32(h, N * H), P_F32_EQ(qk, K * H), P_F32_EQ(cb, K),
+      P_F32(mask, N * K), P_F32_EQ(Wv, K * H * H), P_F32_EQ(bv, K * H),
+      P_F32_EQ(Wl, H * H), P_F32_EQ(bl, H), P_F32_EQ(wmu, H),
+      P_F32_EQ(bmu, 1), P_F32_EQ(wsig, H), P_F32_EQ(bsig, 1),
+      P_F32(a, N * K), P_F32(sd, N * K), P_I32(guard, K), P_F32(u, K * H),
+      P_F32(ctx, K * H), P_F32(hm2, K * H), P_F32(pmu, K),
+      P_F32(psig_pre, K), P_F32(psig, K), P_F32(psig_c, K), N, K, H,
+      (float)alpha, (float)keep_inv, variant, cur_stream()));
+}
+
+// q / bk (K,H), Wk (K,H,H) and their gradients; hpart K * (2H + 2) floats.
+// In-kernel KL gradients: kl_* all four or none; dpmu and dpsig_c are then
+// outputs.
+void attn_fused_bwd(Tensor dpmu, Tensor dpsig_c, Tensor psig,
+                    Tensor psig_pre, Tensor hm2, Tensor wmu, Tensor wsig,
+                    Tensor Wl, Tensor h, Tensor a, Tensor sd, OptTensor mask,
+                    Tensor guard, Tensor u, Tensor Wv, Tensor q, Tensor Wk,
+                    Tensor bk, Tensor dz2, Tensor du, Tensor ds, Tensor dc,
+                    Tensor dWv, Tensor dbv, Tensor dq, Tensor dWk, Tensor dbk,
+                    Tensor hpart, Tensor dwmu, Tensor dbmu, Tensor dwsig,
+                    Tensor dbsig, double alpha, double keep_inv, int variant,
+                    OptTensor kl_fmu = c10::nullopt,
+                    OptTensor kl_fsig_c = c10::nullopt,
+                    OptTensor kl_pmu = c10::nullopt,
+                    OptTensor kl_psig_c = c10::nullopt,
+                    double kl_gscale = 1.0) {
+  OP("attn_fused_bwd", dpmu);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(q, 0);
+  op.require(DIM(q, 1) == H, "q must be (K,H)");
+  op.require(kl_fmu.has_value() == kl_fsig_c.has_value() &&
+                 kl_fmu.has_value() == kl_pmu.has_value() &&
+                 kl_fmu.has_value() == kl_psig_c.has_value(),
+             "kl_* come as a set of four");
+  RUN(fv_attn_fused_bwd(
+      P_F32(dpmu, K), P_F32(dpsig_c, K), P_F32(psig, K), P_F32(psig_pre, K),
+      P_F32(hm2, K * H), P_F32_EQ(wmu, H), P_F32_EQ(wsig, H),
+      P_F32_EQ(Wl, H * H), P_F32(h, N * H), P_F32(a, N * K), P_F32(sd, N * K),
+      P_F32(mask, N * K), P_I32(guard, K), P_F32(u, K * H),
+      P_F32_EQ(Wv, K * H * H), P_F32_EQ(q, K * H), P_F32_EQ(Wk, K * H * H),
+      P_F32_EQ(bk, K * H), P_F32(dz2, K * H), P_F32(du, K * H),
+      P_F32(ds, N * K), P_F32(dc, K), P_F32_EQ(dWv, K * H * H),
+      P_F32_EQ(dbv, K * H), P_F32_EQ(dq, K * H), P_F32_EQ(dWk, K * H * H),
+      P_F32_EQ(dbk, K * H), P_F32(hpart, K * (2 * H + 2)), P_F32_EQ(dwmu, H),
+      P_F32_EQ(dbmu, 1), P_F32_EQ(dwsig, H), P_F32_EQ(dbsig, 1), N, K, H,
+      (float)alpha, (float)keep_inv, variant, P_F32(kl_fmu, K),
+      P_F32(kl_fsig_c, K), P_F32(kl_pmu, K), P_F32(kl_psig_c, K),
+      (float)kl_gscale, cur_stream()));
+}
+
+void attn_qk_fwd(Tensor q, Tensor Wk, Tensor bk, Tensor qk, Tensor c) {
+  OP("attn_qk_fwd", q);
+  const long K = DIM(q, 0), H = DIM(q, 1);
+  RUN(fv_attn_qk_fwd(P_F32_EQ(q, K * H), P_F32_EQ(Wk, K * H * H),
+                     P_F32_EQ(bk, K * H), P_F32(qk, K * H), P_F32(c, K), K, H,
+                     cur_stream()));
+}
+
+void attn_softmax_fwd(Tensor s, OptTensor mask, Tensor a, Tensor sd,
+                      Tensor guard, double keep_inv) {
+  OP("attn_softmax_fwd", s);
+  const long N = DIM(s, 0), K = DIM(s, 1);
+  RUN(fv_attn_softmax_fwd(P_F32(s, N * K), P_F32(mask, N * K),
+                          P_F32(a, N * K), P_F32(sd, N * K), P_I32(guard, K),
+                          N, K, (float)keep_inv, cur_stream()));
+}
+
+void attn_ctx_fwd(Tensor u, Tensor Wv, Tensor bv, Tensor guard, Tensor ctx) {
+  OP("attn_ctx_fwd", u);
+  const long K = DIM(u, 0), H = DIM(u, 1);
+  RUN(fv_attn_ctx_fwd(P_F32(u, K * H), P_F32_EQ(Wv, K * H * H),
+                      P_F32_EQ(bv, K * H), P_I32(guard, K), P_F32(ctx, K * H),
+                      K, H, cur_stream()));
+}
+
+void attn_head_bwd(Tensor dctx, Tensor u, Tensor Wv, Tensor guard, Tensor du,
+                   Tensor dWv, Tensor dbv) {
+  OP("attn_head_bwd", dctx);
+  const long K = DIM(u, 0), H = DIM(u, 1);
+  RUN(fv_attn_head_bwd(P_F32(dctx, K * H), P_F32(u, K * H),
+                       P_F32_EQ(Wv, K * H * H), P_I32(guard, K),
+                       P_F32(du, K * H), P_F32_EQ(dWv, K * H * H),
+                       P_F32_EQ(dbv, K * H), K, H, cur_stream()));
+}
+
+void attn_softmax_bwd(Tensor da, Tensor a, Tensor sd, OptTensor mask,
+                      Tensor guard, Tensor ds, Tensor dc, double keep_inv,
                       double alpha) {
-  CK(da); CK(a); CK(sd); CK(ds); CK(dc);
-  const float* mp = nullptr;
-  if (mask.has_value()) { CK(*mask); mp = fp(*mask); }
-  RUN(fv_attn_softmax_bwd(fp(da), fp(a), fp(sd), mp, guard.data_ptr<int>(),
-                          fpm(ds), fpm(dc), a.size(0), a.size(1),
+  OP("attn_softmax_bwd", da);
+  const long N = DIM(a, 0), K = DIM(a, 1);
+  RUN(fv_attn_softmax_bwd(P_F32(da, N * K), P_F32(a, N * K), P_F32(sd, N * K),
+                          P_F32(mask, N * K), P_I32(guard, K),
+                          P_F32(ds, N * K), P_F32(dc, K), N, K,
                           (float)keep_inv, (float)alpha, cur_stream()));
 }
 
-void attn_qk_bwd(torch::Tensor dqk, torch::Tensor dc, torch::Tensor q,
-                 torch::Tensor Wk, torch::Tensor bk, torch::Tensor dq,
-                 torch::Tensor dWk, torch::Tensor dbk) {
-  CK(dqk); CK(dc); CK(q); CK(Wk); CK(bk); CK(dq); CK(dWk); CK(dbk);
-  RUN(fv_attn_qk_bwd(fp(dqk), fp(dc), fp(q), fp(Wk), fp(bk), fpm(dq),
-                     fpm(dWk), fpm(dbk), q.size(0), q.size(1), cur_stream()));
+void attn_qk_bwd(Tensor dqk, Tensor dc, Tensor q, Tensor Wk, Tensor bk,
+                 Tensor dq, Tensor dWk, Tensor dbk) {
+  OP("attn_qk_bwd", dqk);
+  const long K = DIM(q, 0), H = DIM(q, 1);
+  RUN(fv_attn_qk_bwd(P_F32(dqk, K * H), P_F32(dc, K), P_F32_EQ(q, K * H),
+                     P_F32_EQ(Wk, K * H * H), P_F32_EQ(bk, K * H),
+                     P_F32_EQ(dq, K * H), P_F32_EQ(dWk, K * H * H),
+                     P_F32_EQ(dbk, K * H), K, H, cur_stream()));
 }
 
-void pred_mlp_fwd(torch::Tensor ctx, torch::Tensor Wl, torch::Tensor bl,
-                  torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
-                  torch::Tensor bsig, torch::Tensor hm2, torch::Tensor pmu,
-                  torch::Tensor psig_pre, torch::Tensor psig,
-                  torch::Tensor psig_c) {
-  CK(ctx); CK(Wl); CK(bl); CK(wmu); CK(bmu); CK(wsig); CK(bsig); CK(hm2);
-  CK(pmu); CK(psig_pre); CK(psig); CK(psig_c);
-  RUN(fv_pred_mlp_fwd(fp(ctx), fp(Wl), fp(bl), fp(wmu), fp(bmu), fp(wsig),
-                      fp(bsig), fpm(hm2), fpm(pmu), fpm(psig_pre), fpm(psig),
-                      fpm(psig_c), ctx.size(0), ctx.size(1), cur_stream()));
+void pred_mlp_fwd(Tensor ctx, Tensor Wl, Tensor bl, Tensor wmu, Tensor bmu,
+                  Tensor wsig, Tensor bsig, Tensor hm2, Tensor pmu,
+                  Tensor psig_pre, Tensor psig, Tensor psig_c) {
+  OP("pred_mlp_fwd", ctx);
+  const long K = DIM(ctx, 0), H = DIM(ctx, 1);
+  RUN(fv_pred_mlp_fwd(P_F32(ctx, K * H), P_F32_EQ(Wl, H * H), P_F32_EQ(bl, H),
+                      P_F32_EQ(wmu, H), P_F32_EQ(bmu, 1), P_F32_EQ(wsig, H),
+                      P_F32_EQ(bsig, 1), P_F32(hm2, K * H), P_F32(pmu, K),
+                      P_F32(psig_pre, K), P_F32(psig, K), P_F32(psig_c, K), K,
+                      H, cur_stream()));
 }
 
-void pred_mlp_bwd(torch::Tensor dpmu, torch::Tensor dpsig_c, torch::Tensor psig,
-                  torch::Tensor psig_pre, torch::Tensor hm2, torch::Tensor wmu,
-                  torch::Tensor wsig, torch::Tensor dz2, torch::Tensor hpart,
-                  torch::Tensor dwmu, torch::Tensor dbmu, torch::Tensor dwsig,
-                  torch::Tensor dbsig) {
-  CK(dpmu); CK(dpsig_c); CK(psig); CK(psig_pre); CK(hm2); CK(wmu); CK(wsig);
-  CK(dz2); CK(hpart); CK(dwmu); CK(dbmu); CK(dwsig); CK(dbsig);
-  TORCH_CHECK(hpart.numel() >= (long)hm2.size(0) * (2 * hm2.size(1) + 2));
-  RUN(fv_pred_mlp_bwd(fp(dpmu), fp(dpsig_c), fp(psig), fp(psig_pre), fp(hm2),
-                      fp(wmu), fp(wsig), fpm(dz2), fpm(hpart), fpm(dwmu),
-                      fpm(dbmu), fpm(dwsig), fpm(dbsig), hm2.size(0),
-                      hm2.size(1), cur_stream()));
+void pred_mlp_bwd(Tensor dpmu, Tensor dpsig_c, Tensor psig, Tensor psig_pre,
+                  Tensor hm2, Tensor wmu, Tensor wsig, Tensor dz2,
+                  Tensor hpart, Tensor dwmu, Tensor dbmu, Tensor dwsig,
+                  Tensor dbsig) {
+  OP("pred_mlp_bwd", dpmu);
+  const long K = DIM(hm2, 0), H = DIM(hm2, 1);
+  RUN(fv_pred_mlp_bwd(P_F32(dpmu, K), P_F32(dpsig_c, K), P_F32(psig, K),
+                      P_F32(psig_pre, K), P_F32(hm2, K * H), P_F32_EQ(wmu, H),
+                      P_F32_EQ(wsig, H), P_F32(dz2, K * H),
+                      P_F32(hpart, K * (2 * H + 2)), P_F32_EQ(dwmu, H),
+                      P_F32_EQ(dbmu, 1), P_F32_EQ(dwsig, H),
+                      P_F32_EQ(dbsig, 1), K, H, cur_stream()));
 }
 
-void dec_fwd(torch::Tensor h, torch::Tensor W1, torch::Tensor b1,
-             torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
-             torch::Tensor bsig, torch::Tensor Wb, torch::Tensor bb,
-             torch::Tensor fmu, torch::Tensor fsig_c, torch::Tensor eps,
-             torch::Tensor recon, torch::Tensor a1, torch::Tensor beta,
-             torch::Tensor asig_pre, torch::Tensor sigma) {
-  CK(h); CK(W1); CK(b1); CK(Wb); CK(bb); CK(fmu); CK(fsig_c); CK(eps);
-  CK(recon); CK(a1); CK(beta); CK(asig_pre); CK(sigma);
-  RUN(fv_dec_fwd(fp(h), fp(W1), fp(b1), fp(wmu), fp(bmu), fp(wsig), fp(bsig),
-                 fp(Wb), fp(bb), fp(fmu), fp(fsig_c), fp(eps), fpm(recon),
-                 fpm(a1), fpm(beta), fpm(asig_pre), fpm(sigma), h.size(0),
-                 Wb.size(0), h.size(1), cur_stream()));
+void dh_combine(Tensor dh, Tensor ds, Tensor qk, Tensor a, Tensor du,
+                Tensor dscores, Tensor Wenc) {
+  OP("dh_combine", dh);
+  const long N = DIM(dh, 0), H = DIM(dh, 1);
+  const long K = DIM(qk, 0), M = DIM(Wenc, 0);
+  op.require(DIM(ds, 0) == N && DIM(ds, 1) == K, "ds must be (N,K)");
+  op.require(a.sizes() == ds.sizes(), "a must be (N,K)");
+  op.require(du.sizes() == qk.sizes(), "du must be (K,H)");
+  op.require(DIM(dscores, 0) == N && DIM(dscores, 1) == M,
+             "dscores must be (N,M)");
+  op.require(DIM(Wenc, 1) == H && DIM(qk, 1) == H, "Wenc / qk must have H columns");
+  RUN(fv_dh_combine(P_F32(dh, N * H), P_F32(ds, N * K), P_F32(qk, K * H),
+                    P_F32(a, N * K), P_F32(du, K * H), P_F32(dscores, N * M),
+                    P_F32_EQ(Wenc, M * H), N, K, M, H, cur_stream()));
+}
+
+// -------------------------------------------------------------- encoder
+// h (N,H); Wenc (M,H); scores / a (N,M); yp (M); the heads Wmu / Wsig (K,M),
+// bmu / bsig (K) write fmu ... fsig_c (K) and need the int32 done counter
+void enc_fused_fwd(Tensor h, Tensor Wenc, Tensor benc, Tensor y,
+                   Tensor scores, Tensor a, Tensor yp,
+                   OptTensor Wmu = c10::nullopt, OptTensor bmu = c10::nullopt,
+                   OptTensor Wsig = c10::nullopt,
+                   OptTensor bsig = c10::nullopt,
+                   OptTensor fmu = c10::nullopt,
+                   OptTensor fsig_pre = c10::nullopt,
+                   OptTensor fsig = c10::nullopt,
+                   OptTensor fsig_c = c10::nullopt,
+                   OptTensor done = c10::nullopt, int variant = 1) {
+  OP("enc_fused_fwd", h);
+  const long N = DIM(h, 0), H = DIM(h, 1), M = DIM(Wenc, 0);
+  const bool heads = fmu.has_value();
+  op.require(!heads || (Wmu.has_value() && bmu.has_value() &&
+                        Wsig.has_value() && bsig.has_value() &&
+                        fsig_pre.has_value() && fsig.has_value() &&
+                        fsig_c.has_value() && done.has_value()),
+             "fused heads need Wmu, bmu, Wsig, bsig, the four outputs and "
+             "an int32 done counter");
+  // without fmu the head arguments are not looked at
+  const long K = heads ? op.num(fmu->numel(), "fmu") : 0;
+  const float *wm = nullptr, *bm = nullptr, *ws = nullptr, *bs = nullptr;
+  float *fm = nullptr, *fsp = nullptr, *fs = nullptr, *fsc = nullptr;
+  int* dn = nullptr;
+  if (heads) {
+    wm = P_F32_EQ(Wmu, K * M); bm = P_F32_EQ(bmu, K);
+    ws = P_F32_EQ(Wsig, K * M); bs = P_F32_EQ(bsig, K);
+    fm = P_F32(fmu, K); fsp = P_F32(fsig_pre, K); fs = P_F32(fsig, K);
+    fsc = P_F32(fsig_c, K); dn = P_I32(done, 1);
+  }
+  RUN(fv_enc_fused_fwd(P_F32(h, N * H), P_F32_EQ(Wenc, M * H),
+                       P_F32_EQ(benc, M), P_F32(y, N), P_F32(scores, N * M),
+                       P_F32(a, N * M), P_F32(yp, M), wm, bm, ws, bs, fm, fsp,
+                       fs, fsc, dn, K, N, M, H, variant, cur_stream()));
+}
+
+void enc_bwd_fused(Tensor dfmu, Tensor dfsig_c, Tensor fsig, Tensor fsig_pre,
+                   Tensor yp, Tensor Wmu, Tensor Wsig, Tensor a, Tensor y,
+                   Tensor dscores, Tensor dWmu, Tensor dbmu, Tensor dWsig,
+                   Tensor dbsig) {
+  OP("enc_bwd_fused", dfmu);
+  const long N = DIM(a, 0), M = DIM(a, 1), K = DIM(Wmu, 0);
+  RUN(fv_enc_bwd_fused(P_F32(dfmu, K), P_F32(dfsig_c, K), P_F32(fsig, K),
+                       P_F32(fsig_pre, K), P_F32(yp, M), P_F32_EQ(Wmu, K * M),
+                       P_F32_EQ(Wsig, K * M), P_F32(a, N * M), P_F32(y, N),
+                       P_F32(dscores, N * M), P_F32(dWmu, K * M),
+                       P_F32(dbmu, K), P_F32(dWsig, K * M), P_F32(dbsig, K),
+                       N, M, K, cur_stream()));
+}
+
+// enc_bwd_fused that forms dfmu / dfsig_c itself from the KL inputs and the
+// decoder's nblk block partials; dfmu and dfsig_c are outputs
+void enc_bwd_mid(Tensor part, long nblk, Tensor fmu, Tensor fsig_c,
+                 Tensor pmu, Tensor psig_c, Tensor fsig, Tensor fsig_pre,
+                 Tensor yp, Tensor Wmu, Tensor Wsig, Tensor a, Tensor y,
+                 Tensor dscores, Tensor dWmu, Tensor dbmu, Tensor dWsig,
+                 Tensor dbsig, Tensor dfmu, Tensor dfsig_c, double gscale) {
+  OP("enc_bwd_mid", part);
+  const long N = DIM(a, 0), M = DIM(a, 1), K = DIM(Wmu, 0);
+  NUM(nblk);
+  RUN(fv_enc_bwd_mid(
+      P_F32(part, 2 * K * nblk), P_F32(fmu, K), P_F32(fsig_c, K),
+      P_F32(pmu, K), P_F32(psig_c, K), P_F32(fsig, K), P_F32(fsig_pre, K),
+      P_F32(yp, M), P_F32_EQ(Wmu, K * M), P_F32_EQ(Wsig, K * M),
+      P_F32(a, N * M), P_F32(y, N), P_F32(dscores, N * M), P_F32(dWmu, K * M),
+      P_F32(dbmu, K), P_F32(dWsig, K * M), P_F32(dbsig, K), P_F32(dfmu, K),
+      P_F32(dfsig_c, K), nblk, N, M, K, (float)gscale, cur_stream()));
+}
+
+void enc_softmax_fwd(Tensor scores, Tensor y, Tensor a, Tensor yp) {
+  OP("enc_softmax_fwd", scores);
+  const long N = DIM(scores, 0), M = DIM(scores, 1);
+  RUN(fv_enc_softmax_fwd(P_F32(scores, N * M), P_F32(y, N), P_F32(a, N * M),
+                         P_F32(yp, M), N, M, cur_stream()));
+}
+
+void enc_softmax_bwd(Tensor dyp, Tensor a, Tensor y, Tensor dscores) {
+  OP("enc_softmax_bwd", dyp);
+  const long N = DIM(a, 0), M = DIM(a, 1);
+  RUN(fv_enc_softmax_bwd(P_F32(dyp, M), P_F32(a, N * M), P_F32(y, N),
+                         P_F32(dscores, N * M), N, M, cur_stream()));
+}
+
+void enc_heads_fwd(Tensor yp, Tensor Wmu, Tensor bmu, Tensor Wsig,
+                   Tensor bsig, Tensor fmu, Tensor fsig_pre, Tensor fsig,
+                   Tensor fsig_c) {
+  OP("enc_heads_fwd", yp);
+  const long M = NUM(yp.numel()), K = DIM(Wmu, 0);
+  RUN(fv_enc_heads_fwd(P_F32(yp, M), P_F32_EQ(Wmu, K * M), P_F32_EQ(bmu, K),
+                       P_F32_EQ(Wsig, K * M), P_F32_EQ(bsig, K),
+                       P_F32(fmu, K), P_F32(fsig_pre, K), P_F32(fsig, K),
+                       P_F32(fsig_c, K), M, K, cur_stream()));
+}
+
+void enc_heads_bwd(Tensor dfmu, Tensor dfsig_c, Tensor fsig, Tensor fsig_pre,
+                   Tensor yp, Tensor Wmu, Tensor Wsig, Tensor dyp,
+                   Tensor dWmu, Tensor dbmu, Tensor dWsig, Tensor dbsig) {
+  OP("enc_heads_bwd", dfmu);
+  const long M = NUM(yp.numel()), K = DIM(Wmu, 0);
+  RUN(fv_enc_heads_bwd(P_F32(dfmu, K), P_F32(dfsig_c, K), P_F32(fsig, K),
+                       P_F32(fsig_pre, K), P_F32(yp, M), P_F32_EQ(Wmu, K * M),
+                       P_F32_EQ(Wsig, K * M), P_F32(dyp, M),
+                       P_F32(dWmu, K * M), P_F32(dbmu, K), P_F32(dWsig, K * M),
+                       P_F32(dbsig, K), M, K, cur_stream()));
+}
+
+// ------------------------------------------------------------- geometry
+int as_int(const char* fn, long v) {
+  TORCH_CHECK(v >= 0 && v <= INT_MAX, fn, ": ", v,
+              " is outside the range of int");
+  return (int)v;
+}
+
+// launch geometry, owned by the .hip files: callers size buffers with these
+long dec_nblk(long N) { return fv_dec_nblk(as_int("dec_nblk", N)); }
+long gru_wgrad_blocks(long N) {
+  return fv_gru_wgrad_blocks(as_int("gru_wgrad_blocks", N));
+}
+long ln_bwd_yblocks(long R, long C) {
+  TORCH_CHECK(R >= 0, "ln_bwd_yblocks: R = ", R);
+  return fv_ln_bwd_yblocks(R, as_int("ln_bwd_yblocks", C));
+}
+
+// -------------------------------------------------------------- decoder
+// h (N,H); W1 (H,H), b1 / wmu / wsig (H), bmu / bsig (1), Wb (K,H), bb (K);
+// fmu / fsig_c (K); per-row buffers of N, N*H or N*K floats; part holds
+// dec_nblk(N) block partials of 2K + 2H + 2 floats.
+void dec_fwd(Tensor h, Tensor W1, Tensor b1, Tensor wmu, Tensor bmu,
+             Tensor wsig, Tensor bsig, Tensor Wb, Tensor bb, Tensor fmu,
+             Tensor fsig_c, Tensor eps, Tensor recon, Tensor a1, Tensor beta,
+             Tensor asig_pre, Tensor sigma) {
+  OP("dec_fwd", h);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(Wb, 0);
+  op.require(DIM(Wb, 1) == H, "Wb must be (K,H)");
+  RUN(fv_dec_fwd(P_F32(h, N * H), P_F32_EQ(W1, H * H), P_F32_EQ(b1, H),
+                 P_F32_EQ(wmu, H), P_F32_EQ(bmu, 1), P_F32_EQ(wsig, H),
+                 P_F32_EQ(bsig, 1), P_F32_EQ(Wb, K * H), P_F32_EQ(bb, K),
+                 P_F32(fmu, K), P_F32(fsig_c, K), P_F32(eps, N),
+                 P_F32(recon, N), P_F32(a1, N * H), P_F32(beta, N * K),
+                 P_F32(asig_pre, N), P_F32(sigma, N), N, K, H, cur_stream()));
+}
+
+void dec_bwd(Tensor drecon, Tensor h, Tensor a1, Tensor beta,
+             Tensor asig_pre, Tensor sigma, Tensor eps, Tensor fmu,
+             Tensor fsig_c, Tensor W1, Tensor wmu, Tensor wsig, Tensor Wb,
+             Tensor dh, Tensor dz1, Tensor dbeta, Tensor part, Tensor dfmu,
+             Tensor dfsig_c, Tensor dwmu, Tensor dbmu, Tensor dwsig,
+             Tensor dbsig) {
+  OP("dec_bwd", drecon);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(Wb, 0);
+  op.require(DIM(Wb, 1) == H, "Wb must be (K,H)");
+  RUN(fv_dec_bwd(
+      P_F32(drecon, N), P_F32(h, N * H), P_F32(a1, N * H), P_F32(beta, N * K),
+      P_F32(asig_pre, N), P_F32(sigma, N), P_F32(eps, N), P_F32(fmu, K),
+      P_F32(fsig_c, K), P_F32_EQ(W1, H * H), P_F32_EQ(wmu, H),
+      P_F32_EQ(wsig, H), P_F32_EQ(Wb, K * H), P_F32(dh, N * H),
+      P_F32(dz1, N * H), P_F32(dbeta, N * K),
+      P_F32(part, fv_dec_nblk(N) * (2 * K + 2 * H + 2)), P_F32(dfmu, K),
+      P_F32(dfsig_c, K), P_F32_EQ(dwmu, H), P_F32_EQ(dbmu, 1),
+      P_F32_EQ(dwsig, H), P_F32_EQ(dbsig, 1), N, K, H, cur_stream()));
+}
+
+// ---- the training step's middle chain (docs/KERNELS.md)
+void dec_fwd_bwd(Tensor h, Tensor W1, Tensor b1, Tensor wmu, Tensor bmu,
+                 Tensor wsig, Tensor bsig, Tensor Wb, Tensor bb, Tensor fmu,
+                 Tensor fsig_c, Tensor eps, Tensor y, Tensor recon, Tensor a1,
+                 Tensor beta, Tensor asig_pre, Tensor sigma, Tensor drecon,
+                 Tensor dh, Tensor dz1, Tensor dbeta, Tensor part,
+                 double gscale) {
+  OP("dec_fwd_bwd", h);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(Wb, 0);
+  op.require(DIM(Wb, 1) == H, "Wb must be (K,H)");
+  RUN(fv_dec_fwd_bwd(
+      P_F32(h, N * H), P_F32_EQ(W1, H * H), P_F32(b1, H), P_F32(wmu, H),
+      P_F32(bmu, 1), P_F32(wsig, H), P_F32(bsig, 1), P_F32_EQ(Wb, K * H),
+      P_F32(bb, K), P_F32(fmu, K), P_F32(fsig_c, K), P_F32(eps, N),
+      P_F32(y, N), P_F32(recon, N), P_F32(a1, N * H), P_F32(beta, N * K),
+      P_F32(asig_pre, N), P_F32(sigma, N), P_F32(drecon, N),
+      P_F32(dh, N * H), P_F32(dz1, N * H), P_F32(dbeta, N * K),
+      P_F32(part, fv_dec_nblk(N) * (2 * K + 2 * H + 2)), N, K, H,
+      (float)gscale, cur_stream()));
+}
+
+// the 2H+2 decoder head gradients out of dec_fwd_bwd's partials (N rows)
+void dec_bwd_reduce_heads(Tensor part, Tensor dwmu, Tensor dbmu,
+                          Tensor dwsig, Tensor dbsig, long N, long K) {
+  OP("dec_bwd_reduce_heads", part);
+  NUM(N); NUM(K);
+  const long H = NUM(dwmu.numel());
+  op.require(N >= 1 && K >= 1, "needs N >= 1 and K >= 1");
+  RUN(fv_dec_bwd_reduce_heads(
+      P_F32(part, fv_dec_nblk(N) * (2 * K + 2 * H + 2)), P_F32_EQ(dwmu, H),
+      P_F32(dbmu, 1), P_F32_EQ(dwsig, H), P_F32(dbsig, 1), N, K, H,
+      cur_stream()));
+}
+
+// ----------------------------------------------------------------- loss
+// recon / y / drecon hold N floats, the KL inputs and gradients K each
+void loss_fused(Tensor recon, Tensor y, Tensor fmu, Tensor fsig_c, Tensor pmu,
+                Tensor psig_c, Tensor loss, Tensor mse, Tensor kl,
+                Tensor drecon, Tensor dfmu, Tensor dfsig_c, Tensor dpmu,
+                Tensor dpsig_c, double gscale) {
+  OP("loss_fused", recon);
+  const long N = op.num(op.same_numel(recon, "recon", y, "y"), "recon");
+  const long K = op.num(op.same_numel(fmu, "fmu", fsig_c, "fsig_c"), "fmu");
+  RUN(fv_loss_fused(P_F32(recon, N), P_F32(y, N), P_F32(fmu, K),
+                    P_F32(fsig_c, K), P_F32(pmu, K), P_F32(psig_c, K),
+                    P_F32(loss, 1), P_F32(mse, 1), P_F32(kl, 1),
+                    P_F32(drecon, N), P_F32(dfmu, K), P_F32(dfsig_c, K),
+                    P_F32(dpmu, K), P_F32(dpsig_c, K), N, K, (float)gscale,
+                    cur_stream()));
+}
+
+// loss, mse and kl only (loss_fused without its gradient stores)
+void loss_scalars(Tensor recon, Tensor y, Tensor fmu, Tensor fsig_c,
+                  Tensor pmu, Tensor psig_c, Tensor loss, Tensor mse,
+                  Tensor kl) {
+  OP("loss_scalars", recon);
+  const long N = op.num(op.same_numel(recon, "recon", y, "y"), "recon");
+  const long K = op.num(op.same_numel(fmu, "fmu", fsig_c, "fsig_c"), "fmu");
+  RUN(fv_loss_scalars(P_F32(recon, N), P_F32(y, N), P_F32(fmu, K),
+                      P_F32(fsig_c, K), P_F32(pmu, K), P_F32(psig_c, K),
+                      P_F32(loss, 1), P_F32(mse, 1), P_F32(kl, 1), N, K,
+                      cur_stream()));
 }
 
 // ---- batched multi-day scoring ------------------------------------
-inline void check_i32(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
-}
-
-void gru_fwd_infer(torch::Tensor gi, torch::Tensor Whh, torch::Tensor bhh,
-                   torch::Tensor h_final, long N, long T, long H) {
-  CK(gi); CK(Whh); CK(bhh); CK(h_final);
-  TORCH_CHECK(gi.numel() >= N * T * 3 * H && h_final.numel() >= N * H &&
-              Whh.numel() == 3 * H * H && bhh.numel() == 3 * H);
-  RUN(fv_gru_fwd_infer(fp(gi), fp(Whh), fp(bhh), fpm(h_final), (int)N,
-                       (int)T, (int)H, cur_stream()));
-}
-
-void gru_fwd_mfma_infer(torch::Tensor gi, torch::Tensor whh_bf,
-                        torch::Tensor bhh, torch::Tensor h_final, long N,
-                        long T, long H) {
-  CK(gi); CKB(whh_bf); CK(bhh); CK(h_final);
-  TORCH_CHECK(gi.numel() >= N * T * 3 * H && h_final.numel() >= N * H &&
-              whh_bf.numel() == 3 * H * H && bhh.numel() == 3 * H);
-  RUN(fv_gru_fwd_mfma_infer(fp(gi), bfpc(whh_bf), fp(bhh), fpm(h_final),
-                            (int)N, (int)T, (int)H, cur_stream()));
-}
-
 // h (sumN,H) packed days; seg_off int32 (D+1) device row offsets; max_n
 // the longest day (host-side knowledge: sizes the launch's LDS).
 // Outputs pmu / psig_c (D,K) fp32 and guard (D,K) int32.
-void attn_seg_fwd(torch::Tensor h, torch::Tensor seg_off, long max_n,
-                  torch::Tensor qk, torch::Tensor cb, torch::Tensor Wv,
-                  torch::Tensor bv, torch::Tensor Wl, torch::Tensor bl,
-                  torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
-                  torch::Tensor bsig, torch::Tensor pmu, torch::Tensor psig_c,
-                  torch::Tensor guard, double alpha) {
-  CK(h); CK(qk); CK(cb); CK(Wv); CK(bv); CK(Wl); CK(bl); CK(wmu); CK(bmu);
-  CK(wsig); CK(bsig); CK(pmu); CK(psig_c);
-  check_i32(seg_off, "seg_off");
-  check_i32(guard, "guard");
-  TORCH_CHECK(h.dim() == 2 && qk.dim() == 2 && qk.size(1) == h.size(1));
-  const long total = h.size(0), H = h.size(1), K = qk.size(0);
-  const long D = seg_off.numel() - 1;
-  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
-  TORCH_CHECK(H <= 64 && K <= 128, "attn_seg_fwd supports H <= 64, K <= 128");
-  TORCH_CHECK(pmu.numel() >= D * K && psig_c.numel() >= D * K &&
-              guard.numel() >= D * K, "per-day outputs too small");
-  TORCH_CHECK(cb.numel() == K && Wv.numel() == K * H * H &&
-              bv.numel() == K * H && Wl.numel() == H * H && bl.numel() == H &&
-              wmu.numel() == H && wsig.numel() == H);
-  TORCH_CHECK(max_n >= 0 && max_n <= total, "max_n outside the packed rows");
-  RUN(fv_attn_seg_fwd(fp(h), seg_off.data_ptr<int>(), fp(qk), fp(cb), fp(Wv),
-                      fp(bv), fp(Wl), fp(bl), fp(wmu), fp(bmu), fp(wsig),
-                      fp(bsig), fpm(pmu), fpm(psig_c), guard.data_ptr<int>(),
-                      (int)total, (int)D, (int)max_n, (int)K, (int)H,
-                      (float)alpha, cur_stream()));
+void attn_seg_fwd(Tensor h, Tensor seg_off, long max_n, Tensor qk, Tensor cb,
+                  Tensor Wv, Tensor bv, Tensor Wl, Tensor bl, Tensor wmu,
+                  Tensor bmu, Tensor wsig, Tensor bsig, Tensor pmu,
+                  Tensor psig_c, Tensor guard, double alpha) {
+  OP("attn_seg_fwd", h);
+  op.require(h.dim() == 2 && qk.dim() == 2 && qk.size(1) == h.size(1),
+             "want h (total,H), qk (K,H)");
+  const long total = DIM(h, 0), H = DIM(h, 1), K = DIM(qk, 0);
+  const long D = NUM(seg_off.numel()) - 1;
+  op.require(D >= 0, "seg_off needs D+1 entries");
+  op.require(max_n >= 0 && max_n <= total, "max_n outside the packed rows");
+  RUN(fv_attn_seg_fwd(
+      P_F32(h, total * H), P_I32(seg_off, D + 1), P_F32_EQ(qk, K * H),
+      P_F32_EQ(cb, K), P_F32_EQ(Wv, K * H * H), P_F32_EQ(bv, K * H),
+      P_F32_EQ(Wl, H * H), P_F32_EQ(bl, H), P_F32_EQ(wmu, H), P_F32(bmu, 1),
+      P_F32_EQ(wsig, H), P_F32(bsig, 1), P_F32(pmu, D * K),
+      P_F32(psig_c, D * K), P_I32(guard, D * K), total, D, max_n, K, H,
+      (float)alpha, cur_stream()));
 }
 
 // fmu / fsig_c are (D,K): each row takes its own day's factor prior.
 // eps/sample and beta are optional; sample = fma(eps, sigma, mu).
-void dec_seg_fwd(torch::Tensor h, torch::Tensor seg_off, torch::Tensor W1,
-                 torch::Tensor b1, torch::Tensor wmu, torch::Tensor bmu,
-                 torch::Tensor wsig, torch::Tensor bsig, torch::Tensor Wb,
-                 torch::Tensor bb, torch::Tensor fmu, torch::Tensor fsig_c,
-                 c10::optional<torch::Tensor> eps, torch::Tensor mu,
-                 torch::Tensor sigma, c10::optional<torch::Tensor> sample,
-                 c10::optional<torch::Tensor> beta) {
-  CK(h); CK(W1); CK(b1); CK(wmu); CK(bmu); CK(wsig); CK(bsig); CK(Wb);
-  CK(bb); CK(fmu); CK(fsig_c); CK(mu); CK(sigma);
-  check_i32(seg_off, "seg_off");
-  TORCH_CHECK(h.dim() == 2 && Wb.dim() == 2 && Wb.size(1) == h.size(1));
-  const long N = h.size(0), H = h.size(1), K = Wb.size(0);
-  const long D = seg_off.numel() - 1;
-  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
-  TORCH_CHECK(H <= 64 && K <= 128, "dec_seg_fwd supports H <= 64, K <= 128");
-  TORCH_CHECK(W1.numel() == H * H && b1.numel() == H && wmu.numel() == H &&
-              wsig.numel() == H && bb.numel() == K);
-  TORCH_CHECK(fmu.numel() >= D * K && fsig_c.numel() >= D * K);
-  TORCH_CHECK(mu.numel() >= N && sigma.numel() >= N);
-  const float* ep = nullptr; float* sp = nullptr; float* bp = nullptr;
-  if (eps.has_value()) {
-    CK(*eps);
-    TORCH_CHECK(sample.has_value(), "eps needs a sample output");
-    CK(*sample);
-    TORCH_CHECK(eps->numel() >= N && sample->numel() >= N);
-    ep = fp(*eps);
-    sp = fpm(*sample);
-  }
-  if (beta.has_value()) {
-    CK(*beta);
-    TORCH_CHECK(beta->numel() >= N * K);
-    bp = fpm(*beta);
-  }
-  RUN(fv_dec_seg_fwd(fp(h), seg_off.data_ptr<int>(), fp(W1), fp(b1), fp(wmu),
-                     fp(bmu), fp(wsig), fp(bsig), fp(Wb), fp(bb), fp(fmu),
-                     fp(fsig_c), ep, fpm(mu), fpm(sigma), sp, bp, (int)N,
-                     (int)D, (int)K, (int)H, cur_stream()));
+void dec_seg_fwd(Tensor h, Tensor seg_off, Tensor W1, Tensor b1, Tensor wmu,
+                 Tensor bmu, Tensor wsig, Tensor bsig, Tensor Wb, Tensor bb,
+                 Tensor fmu, Tensor fsig_c, OptTensor eps, Tensor mu,
+                 Tensor sigma, OptTensor sample, OptTensor beta) {
+  OP("dec_seg_fwd", h);
+  op.require(h.dim() == 2 && Wb.dim() == 2 && Wb.size(1) == h.size(1),
+             "want h (N,H), Wb (K,H)");
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(Wb, 0);
+  const long D = NUM(seg_off.numel()) - 1;
+  op.require(D >= 0, "seg_off needs D+1 entries");
+  op.require(!eps.has_value() || sample.has_value(),
+             "eps needs a sample output");
+  const float* ep = P_F32(eps, N);
+  RUN(fv_dec_seg_fwd(
+      P_F32(h, N * H), P_I32(seg_off, D + 1), P_F32_EQ(W1, H * H),
+      P_F32_EQ(b1, H), P_F32_EQ(wmu, H), P_F32(bmu, 1), P_F32_EQ(wsig, H),
+      P_F32(bsig, 1), P_F32_EQ(Wb, K * H), P_F32_EQ(bb, K),
+      P_F32(fmu, D * K), P_F32(fsig_c, D * K), ep, P_F32(mu, N),
+      P_F32(sigma, N), ep ? P_F32(sample, N) : nullptr, P_F32(beta, N * K),
+      N, D, K, H, cur_stream()));
 }
 
 // pred (P,total) fp32 rows with any row stride (a row slice of the scoring
@@ -1233,227 +1027,44 @@ void dec_seg_fwd(torch::Tensor h, torch::Tensor seg_off, torch::Tensor W1,
 // max_n the longest day (sizes the launch's LDS, <= 8192). Outputs, fully
 // written: stats (D,P,4) float64 = ic, rank_ic, long, short; count (D,P)
 // int32 = valid rows, -1 for a refused segment.
-void daily_ic_seg(torch::Tensor pred, torch::Tensor label,
-                  torch::Tensor seg_off, long max_n, long topk,
-                  torch::Tensor stats, torch::Tensor count) {
-  TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == torch::kFloat32,
-              "pred must be fp32 on GPU");
-  TORCH_CHECK(pred.dim() == 2, "pred must be (P, total)");
-  const long P = pred.size(0), total = pred.size(1);
-  TORCH_CHECK(P >= 1, "pred needs at least one row");
-  TORCH_CHECK(total <= 1 || pred.stride(1) == 1,
-              "pred rows must be contiguous");
-  TORCH_CHECK(P == 1 || pred.stride(0) >= 0);
-  CK(label);
-  check_i32(seg_off, "seg_off");
-  check_i32(count, "count");
-  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() &&
-              stats.scalar_type() == torch::kFloat64,
-              "stats must be contiguous float64 on GPU");
-  const long D = seg_off.numel() - 1;
-  TORCH_CHECK(D >= 0, "seg_off needs D+1 entries");
-  TORCH_CHECK(label.numel() >= total, "label shorter than the packed rows");
-  TORCH_CHECK(total < (1L << 31), "too many packed rows");
-  TORCH_CHECK(stats.numel() >= D * P * 4 && count.numel() >= D * P,
-              "per-day outputs too small");
-  TORCH_CHECK(max_n >= 0 && max_n <= 8192,
-              "daily_ic_seg supports days of up to 8192 rows, got max_n=",
-              max_n);
-  TORCH_CHECK(topk >= 0 && topk < (1L << 31), "topk out of range");
-  RUN(fv_daily_ic_seg(fp(pred), P > 1 ? (long)pred.stride(0) : 0L, fp(label),
-                      seg_off.data_ptr<int>(), stats.data_ptr<double>(),
-                      count.data_ptr<int>(), (int)total, (int)D, (int)P,
-                      (int)max_n, (int)topk, cur_stream()));
+void daily_ic_seg(Tensor pred, Tensor label, Tensor seg_off, long max_n,
+                  long topk, Tensor stats, Tensor count) {
+  OP("daily_ic_seg", pred);
+  // pred is the one strided argument: its own checks
+  op.require(pred.is_cuda() && pred.scalar_type() == torch::kFloat32,
+             "pred must be fp32 on GPU");
+  op.require(pred.dim() == 2, "pred must be (P, total)");
+  const long P = DIM(pred, 0), total = DIM(pred, 1);
+  op.require(P >= 1, "pred needs at least one row");
+  op.require(total <= 1 || pred.stride(1) == 1,
+             "pred rows must be contiguous");
+  op.require(P == 1 || pred.stride(0) >= 0, "pred row stride is negative");
+  const long D = NUM(seg_off.numel()) - 1;
+  op.require(D >= 0, "seg_off needs D+1 entries");
+  op.require(max_n >= 0 && max_n <= 8192,
+             "supports days of up to 8192 rows, got max_n=", max_n);
+  NUM(topk);
+  RUN(fv_daily_ic_seg(pred.data_ptr<float>(),
+                      P > 1 ? (long)pred.stride(0) : 0L, P_F32(label, total),
+                      P_I32(seg_off, D + 1), P_F64(stats, D * P * 4),
+                      P_I32(count, D * P), total, D, P, max_n, topk,
+                      cur_stream()));
 }
 
-void dec_bwd(torch::Tensor drecon, torch::Tensor h, torch::Tensor a1,
-             torch::Tensor beta, torch::Tensor asig_pre, torch::Tensor sigma,
-             torch::Tensor eps, torch::Tensor fmu, torch::Tensor fsig_c,
-             torch::Tensor W1, torch::Tensor wmu, torch::Tensor wsig,
-             torch::Tensor Wb, torch::Tensor dh, torch::Tensor dz1,
-             torch::Tensor dbeta, torch::Tensor part, torch::Tensor dfmu,
-             torch::Tensor dfsig_c, torch::Tensor dwmu, torch::Tensor dbmu,
-             torch::Tensor dwsig, torch::Tensor dbsig) {
-  CK(drecon); CK(h); CK(a1); CK(beta); CK(asig_pre); CK(sigma); CK(eps);
-  CK(fmu); CK(fsig_c); CK(W1); CK(wmu); CK(wsig); CK(Wb); CK(dh); CK(dz1);
-  CK(dbeta); CK(part); CK(dfmu); CK(dfsig_c); CK(dwmu); CK(dbmu); CK(dwsig);
-  CK(dbsig);
-  const int N_ = h.size(0), K_ = Wb.size(0), H_ = h.size(1);
-  long iters = (N_ + 4 * 128 - 1) / (4 * 128);
-  if (iters > 8) iters = 8;
-  if (iters < 1) iters = 1;
-  const long nblk = (N_ + 4 * iters - 1) / (4 * iters);
-  TORCH_CHECK(part.numel() >= nblk * (2 * K_ + 2 * H_ + 2));
-  RUN(fv_dec_bwd(fp(drecon), fp(h), fp(a1), fp(beta), fp(asig_pre), fp(sigma),
-                 fp(eps), fp(fmu), fp(fsig_c), fp(W1), fp(wmu), fp(wsig),
-                 fp(Wb), fpm(dh), fpm(dz1), fpm(dbeta), fpm(part), fpm(dfmu),
-                 fpm(dfsig_c), fpm(dwmu), fpm(dbmu), fpm(dwsig), fpm(dbsig),
-                 N_, K_, H_, cur_stream()));
+// ------------------------------------------------------------ optimizer
+void step_inc(Tensor step_t) {
+  OP("step_inc", step_t);
+  RUN(fv_step_inc(P_I32(step_t, 1), cur_stream()));
 }
 
-void loss_fwd(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
-              torch::Tensor fsig_c, torch::Tensor pmu, torch::Tensor psig_c,
-              torch::Tensor loss, torch::Tensor mse, torch::Tensor kl) {
-  CK(recon); CK(y); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(loss);
-  CK(mse); CK(kl);
-  RUN(fv_loss_fwd(fp(recon), fp(y), fp(fmu), fp(fsig_c), fp(pmu), fp(psig_c),
-                  fpm(loss), fpm(mse), fpm(kl), recon.numel(), fmu.numel(),
-                  cur_stream()));
-}
-
-void loss_bwd(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
-              torch::Tensor fsig_c, torch::Tensor pmu, torch::Tensor psig_c,
-              torch::Tensor drecon, torch::Tensor dfmu, torch::Tensor dfsig_c,
-              torch::Tensor dpmu, torch::Tensor dpsig_c, double gscale) {
-  CK(recon); CK(y); CK(drecon); CK(dfmu); CK(dfsig_c); CK(dpmu); CK(dpsig_c);
-  RUN(fv_loss_bwd(fp(recon), fp(y), fp(fmu), fp(fsig_c), fp(pmu), fp(psig_c),
-                  fpm(drecon), fpm(dfmu), fpm(dfsig_c), fpm(dpmu),
-                  fpm(dpsig_c), recon.numel(), fmu.numel(), (float)gscale,
-                  cur_stream()));
-}
-
-void loss_fused(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
-                torch::Tensor fsig_c, torch::Tensor pmu, torch::Tensor psig_c,
-                torch::Tensor loss, torch::Tensor mse, torch::Tensor kl,
-                torch::Tensor drecon, torch::Tensor dfmu,
-                torch::Tensor dfsig_c, torch::Tensor dpmu,
-                torch::Tensor dpsig_c, double gscale) {
-  CK(recon); CK(y); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(loss);
-  CK(mse); CK(kl); CK(drecon); CK(dfmu); CK(dfsig_c); CK(dpmu); CK(dpsig_c);
-  RUN(fv_loss_fused(fp(recon), fp(y), fp(fmu), fp(fsig_c), fp(pmu),
-                    fp(psig_c), fpm(loss), fpm(mse), fpm(kl), fpm(drecon),
-                    fpm(dfmu), fpm(dfsig_c), fpm(dpmu), fpm(dpsig_c),
-                    recon.numel(), fmu.numel(), (float)gscale, cur_stream()));
-}
-
-// ---- the training step's middle chain --------------------------------
-inline long dec_nblk(long N) {
-  long iters = (N + 4 * 128 - 1) / (4 * 128);
-  if (iters > 8) iters = 8;
-  if (iters < 1) iters = 1;
-  return (N + 4 * iters - 1) / (4 * iters);
-}
-
-void dec_fwd_bwd(torch::Tensor h, torch::Tensor W1, torch::Tensor b1,
-                 torch::Tensor wmu, torch::Tensor bmu, torch::Tensor wsig,
-                 torch::Tensor bsig, torch::Tensor Wb, torch::Tensor bb,
-                 torch::Tensor fmu, torch::Tensor fsig_c, torch::Tensor eps,
-                 torch::Tensor y, torch::Tensor recon, torch::Tensor a1,
-                 torch::Tensor beta, torch::Tensor asig_pre,
-                 torch::Tensor sigma, torch::Tensor drecon, torch::Tensor dh,
-                 torch::Tensor dz1, torch::Tensor dbeta, torch::Tensor part,
-                 double gscale) {
-  CK(h); CK(W1); CK(b1); CK(wmu); CK(bmu); CK(wsig); CK(bsig); CK(Wb); CK(bb);
-  CK(fmu); CK(fsig_c); CK(eps); CK(y); CK(recon); CK(a1); CK(beta);
-  CK(asig_pre); CK(sigma); CK(drecon); CK(dh); CK(dz1); CK(dbeta); CK(part);
-  const long N = h.size(0), H = h.size(1), K = Wb.size(0);
-  TORCH_CHECK(H >= 1 && H <= 64 && K >= 1 && K <= 128 && N >= 1,
-              "dec_fwd_bwd: H <= 64, K <= 128");
-  TORCH_CHECK(W1.numel() == H * H && Wb.numel() == K * H && b1.numel() >= H &&
-              wmu.numel() >= H && wsig.numel() >= H && bb.numel() >= K &&
-              fmu.numel() >= K && fsig_c.numel() >= K && bmu.numel() >= 1 &&
-              bsig.numel() >= 1, "dec_fwd_bwd: parameter sizes");
-  TORCH_CHECK(eps.numel() >= N && y.numel() >= N && recon.numel() >= N &&
-              asig_pre.numel() >= N && sigma.numel() >= N &&
-              drecon.numel() >= N && a1.numel() >= N * H &&
-              dh.numel() >= N * H && dz1.numel() >= N * H &&
-              beta.numel() >= N * K && dbeta.numel() >= N * K,
-              "dec_fwd_bwd: row buffer sizes");
-  TORCH_CHECK(part.numel() >= dec_nblk(N) * (2 * K + 2 * H + 2));
-  RUN(fv_dec_fwd_bwd(fp(h), fp(W1), fp(b1), fp(wmu), fp(bmu), fp(wsig),
-                     fp(bsig), fp(Wb), fp(bb), fp(fmu), fp(fsig_c), fp(eps),
-                     fp(y), fpm(recon), fpm(a1), fpm(beta), fpm(asig_pre),
-                     fpm(sigma), fpm(drecon), fpm(dh), fpm(dz1), fpm(dbeta),
-                     fpm(part), (int)N, (int)K, (int)H, (float)gscale,
-                     cur_stream()));
-}
-
-// the 2H+2 decoder head gradients out of dec_fwd_bwd's partials (N rows)
-void dec_bwd_reduce_heads(torch::Tensor part, torch::Tensor dwmu,
-                          torch::Tensor dbmu, torch::Tensor dwsig,
-                          torch::Tensor dbsig, long N, long K) {
-  CK(part); CK(dwmu); CK(dbmu); CK(dwsig); CK(dbsig);
-  const long H = dwmu.numel();
-  TORCH_CHECK(dwsig.numel() == H && dbmu.numel() >= 1 && dbsig.numel() >= 1);
-  TORCH_CHECK(N >= 1 && K >= 1 &&
-              part.numel() >= dec_nblk(N) * (2 * K + 2 * H + 2));
-  RUN(fv_dec_bwd_reduce_heads(fp(part), fpm(dwmu), fpm(dbmu), fpm(dwsig),
-                              fpm(dbsig), (int)N, (int)K, (int)H,
-                              cur_stream()));
-}
-
-// enc_bwd_fused that forms dfmu / dfsig_c itself from the KL inputs and the
-// decoder's nblk block partials; dfmu and dfsig_c are outputs
-void enc_bwd_mid(torch::Tensor part, long nblk, torch::Tensor fmu,
-                 torch::Tensor fsig_c, torch::Tensor pmu,
-                 torch::Tensor psig_c, torch::Tensor fsig,
-                 torch::Tensor fsig_pre, torch::Tensor yp, torch::Tensor Wmu,
-                 torch::Tensor Wsig, torch::Tensor a, torch::Tensor y,
-                 torch::Tensor dscores, torch::Tensor dWmu,
-                 torch::Tensor dbmu, torch::Tensor dWsig, torch::Tensor dbsig,
-                 torch::Tensor dfmu, torch::Tensor dfsig_c, double gscale) {
-  CK(part); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(fsig); CK(fsig_pre);
-  CK(yp); CK(Wmu); CK(Wsig); CK(a); CK(y); CK(dscores); CK(dWmu); CK(dbmu);
-  CK(dWsig); CK(dbsig); CK(dfmu); CK(dfsig_c);
-  const long N = a.size(0), M = a.size(1), K = Wmu.size(0);
-  TORCH_CHECK(K >= 1 && K <= 256 && nblk >= 1 && M >= 1,
-              "enc_bwd_mid: K <= 256");
-  TORCH_CHECK(part.numel() >= 2 * K * nblk, "enc_bwd_mid: part size");
-  TORCH_CHECK(fmu.numel() >= K && fsig_c.numel() >= K && pmu.numel() >= K &&
-              psig_c.numel() >= K && fsig.numel() >= K &&
-              fsig_pre.numel() >= K && dfmu.numel() >= K &&
-              dfsig_c.numel() >= K && dbmu.numel() >= K &&
-              dbsig.numel() >= K && yp.numel() >= M && y.numel() >= N &&
-              Wmu.numel() == K * M && Wsig.numel() == K * M &&
-              dWmu.numel() >= K * M && dWsig.numel() >= K * M &&
-              dscores.numel() >= N * M, "enc_bwd_mid: sizes");
-  RUN(fv_enc_bwd_mid(fp(part), fp(fmu), fp(fsig_c), fp(pmu), fp(psig_c),
-                     fp(fsig), fp(fsig_pre), fp(yp), fp(Wmu), fp(Wsig), fp(a),
-                     fp(y), fpm(dscores), fpm(dWmu), fpm(dbmu), fpm(dWsig),
-                     fpm(dbsig), fpm(dfmu), fpm(dfsig_c), (int)nblk, (int)N,
-                     (int)M, (int)K, (float)gscale, cur_stream()));
-}
-
-// loss, mse and kl only (loss_fused without its gradient stores)
-void loss_scalars(torch::Tensor recon, torch::Tensor y, torch::Tensor fmu,
-                  torch::Tensor fsig_c, torch::Tensor pmu,
-                  torch::Tensor psig_c, torch::Tensor loss, torch::Tensor mse,
-                  torch::Tensor kl) {
-  CK(recon); CK(y); CK(fmu); CK(fsig_c); CK(pmu); CK(psig_c); CK(loss);
-  CK(mse); CK(kl);
-  RUN(fv_loss_scalars(fp(recon), fp(y), fp(fmu), fp(fsig_c), fp(pmu),
-                      fp(psig_c), fpm(loss), fpm(mse), fpm(kl), recon.numel(),
-                      fmu.numel(), cur_stream()));
-}
-
-void dh_combine(torch::Tensor dh, torch::Tensor ds, torch::Tensor qk,
-                torch::Tensor a, torch::Tensor du, torch::Tensor dscores,
-                torch::Tensor Wenc) {
-  CK(dh); CK(ds); CK(qk); CK(a); CK(du); CK(dscores); CK(Wenc);
-  const int N_ = dh.size(0), H_ = dh.size(1);
-  const int K_ = qk.size(0), M_ = Wenc.size(0);
-  TORCH_CHECK(ds.size(0) == N_ && ds.size(1) == K_, "ds shape");
-  TORCH_CHECK(a.sizes() == ds.sizes(), "a shape");
-  TORCH_CHECK(du.sizes() == qk.sizes(), "du shape");
-  TORCH_CHECK(dscores.size(0) == N_ && dscores.size(1) == M_, "dscores");
-  TORCH_CHECK(Wenc.size(1) == H_ && qk.size(1) == H_, "B cols");
-  RUN(fv_dh_combine(fpm(dh), fp(ds), fp(qk), fp(a), fp(du), fp(dscores),
-                    fp(Wenc), N_, K_, M_, H_, cur_stream()));
-}
-
-void step_inc(torch::Tensor step_t) {
-  TORCH_CHECK(step_t.scalar_type() == torch::kInt32 && step_t.is_cuda());
-  RUN(fv_step_inc(step_t.data_ptr<int>(), cur_stream()));
-}
-
-void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
-          torch::Tensor step_t, double lr0, double eta_min, double t_max,
-          double beta1, double beta2, double eps) {
-  CK(p); CK(g); CK(m); CK(v);
-  TORCH_CHECK(step_t.scalar_type() == torch::kInt32 && step_t.is_cuda());
-  RUN(fv_adam(fpm(p), fp(g), fpm(m), fpm(v), step_t.data_ptr<int>(), p.numel(),
-              (float)lr0, (float)eta_min, (float)t_max, (float)beta1,
-              (float)beta2, (float)eps, cur_stream()));
+void adam(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step_t, double lr0,
+          double eta_min, double t_max, double beta1, double beta2,
+          double eps) {
+  OP("adam", p);
+  const int64_t n = op.same_numel(p, "p", g, "g");
+  RUN(fv_adam(P_F32(p, n), P_F32_EQ(g, n), P_F32_EQ(m, n), P_F32_EQ(v, n),
+              P_I32(step_t, 1), n, (float)lr0, (float)eta_min, (float)t_max,
+              (float)beta1, (float)beta2, (float)eps, cur_stream()));
 }
 
 }  // namespace
@@ -1487,7 +1098,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("accumulate"), py::arg("db") = py::none(),
           py::arg("db_part") = py::none());
   mod.def("cast_f32_bf16", &cast_f32_bf16);
-  mod.def("cast3_f32_bf16", &cast3_f32_bf16);
   mod.def("lrelu_bwd_bf16", &lrelu_bwd_bf16);
   mod.def("lrelu_bwd", &lrelu_bwd);
   mod.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("gamma"), py::arg("beta"),
@@ -1543,6 +1153,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("variant") = 1, py::arg("kl_fmu") = py::none(),
           py::arg("kl_fsig_c") = py::none(), py::arg("kl_pmu") = py::none(),
           py::arg("kl_psig_c") = py::none(), py::arg("kl_gscale") = 1.0);
+  // launch geometry the .hip files own: block counts that size buffers
+  mod.def("dec_nblk", &dec_nblk);
+  mod.def("gru_wgrad_blocks", &gru_wgrad_blocks);
+  mod.def("ln_bwd_yblocks", &ln_bwd_yblocks);
   mod.def("dec_fwd_bwd", &dec_fwd_bwd);
   mod.def("dec_bwd_reduce_heads", &dec_bwd_reduce_heads);
   mod.def("enc_bwd_mid", &enc_bwd_mid);
@@ -1614,8 +1228,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("pred"), py::arg("label"), py::arg("seg_off"),
           py::arg("max_n"), py::arg("topk"), py::arg("stats"),
           py::arg("count"));
-  mod.def("loss_fwd", &loss_fwd);
-  mod.def("loss_bwd", &loss_bwd);
   mod.def("step_inc", &step_inc);
   mod.def("adam", &adam);
 }

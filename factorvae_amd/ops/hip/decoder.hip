@@ -12,6 +12,7 @@
 // unit. W1 and Wb staged in LDS transposed for conflict-free lane reads.
 
 #include "common.h"
+#include "launchers.h"
 #include "stage.h"
 
 #define DEC_RPW 4
@@ -547,6 +548,14 @@ static inline void dec_bwd_geometry(int N, int* iters, int* nblk) {
 
 extern "C" {
 
+// the block count alone: it sizes `part`, (2K + 2H + 2) floats per block,
+// and is the nblk that enc_bwd_mid reads those partials with
+int fv_dec_nblk(int N) {
+  int iters, nblk;
+  dec_bwd_geometry(N, &iters, &nblk);
+  return nblk;
+}
+
 hipError_t fv_dec_fwd_bwd(const float* h, const float* W1, const float* b1,
                           const float* wmu, const float* bmu,
                           const float* wsig, const float* bsig,
@@ -611,11 +620,8 @@ hipError_t fv_dec_bwd(const float* drecon, const float* h, const float* a1,
   if (H > 64 || K > 128) return hipErrorInvalidValue;
   const size_t lds = ((size_t)H * H + (size_t)K * H + DEC_RPW * H +
                       (size_t)DEC_RPW * K + 4 * 64) * sizeof(float);
-  // ~128+ blocks to fill the chip; <=8 row-iterations per block
-  int iters = (N + DEC_RPW * 128 - 1) / (DEC_RPW * 128);
-  if (iters > 8) iters = 8;
-  if (iters < 1) iters = 1;
-  const int nblk = (N + DEC_RPW * iters - 1) / (DEC_RPW * iters);
+  int iters, nblk;
+  dec_bwd_geometry(N, &iters, &nblk);
   hipLaunchKernelGGL(dec_bwd_kernel, dim3(nblk), dim3(256), lds, s,
                      drecon, h, a1, beta, asig_pre, sigma, eps, fmu, fsig_c,
                      W1, wmu, wsig, Wb, dh, dz1, dbeta, part, N, K, H, iters);

@@ -6,6 +6,7 @@
 // column m: column softmax over N stocks + weighted return reduction.
 
 #include "common.h"
+#include "launchers.h"
 #include "stage.h"
 
 __global__ __launch_bounds__(256) void enc_softmax_fwd_kernel(

@@ -4,6 +4,7 @@
 // are gemm_nt calls; the GRU recurrence is gru.hip.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -586,6 +587,19 @@ static hipError_t eh_launch(const float* x, const float* gamma,
   return hipSuccess;
 }
 
+// fv_ln_bwd_params' launch geometry. ~2000 blocks: the reduction is
+// latency-bound per block (two global reads per row-iteration), so
+// parallelism beats reduce thrift. Returns the row-chunk count.
+static inline unsigned ln_bwd_geometry(long R, int C, long* rpb_out) {
+  const int cblocks = (C + 63) / 64;
+  long target_y = (2048 + cblocks - 1) / cblocks;
+  long rpb = (R + target_y - 1) / target_y;
+  if (rpb < 64) rpb = 64;
+  if (rpb > 8192) rpb = 8192;
+  *rpb_out = rpb;
+  return (unsigned)((R + rpb - 1) / rpb);
+}
+
 extern "C" {
 
 hipError_t fv_ln_fwd(const float* x, const float* gamma, const float* beta,
@@ -641,20 +655,21 @@ hipError_t fv_extractor_head_fwd(const float* x, const float* gamma,
   return e;
 }
 
+// row chunks of fv_ln_bwd_params; `part` holds 2C floats for each
+int fv_ln_bwd_yblocks(long R, int C) {
+  long rpb;
+  return (int)ln_bwd_geometry(R, C, &rpb);
+}
+
 hipError_t fv_ln_bwd_params(const float* x, const float* dxln,
                             const float* mean, const float* rstd,
                             float* part, float* dgamma, float* dbeta,
                             long R, int C, int r_chunks,
                             hipStream_t stream) {
   (void)r_chunks;
-  // ~2000 blocks: this reduction is latency-bound per block (two global
-  // reads per row-iteration), so parallelism beats reduce thrift
   const int cblocks = (C + 63) / 64;
-  long target_y = (2048 + cblocks - 1) / cblocks;
-  long rpb = (R + target_y - 1) / target_y;
-  if (rpb < 64) rpb = 64;
-  if (rpb > 8192) rpb = 8192;
-  const unsigned yblocks = (unsigned)((R + rpb - 1) / rpb);
+  long rpb;
+  const unsigned yblocks = ln_bwd_geometry(R, C, &rpb);
   dim3 grid(cblocks, yblocks);
   hipLaunchKernelGGL(ln_bwd_params_kernel, grid, dim3(256), 0, stream,
                      x, dxln, mean, rstd, part, R, C, (int)rpb);

@@ -10,6 +10,7 @@
 // to a multiple of 4 bytes so staging can use dword-coalesced loads.
 
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;

@@ -15,6 +15,7 @@
 //   colsum:   out(C)    (+)= sum_r A(R,C)         (bias grads)
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 

@@ -18,6 +18,7 @@
 // [r, z, n, q].
 
 #include "common.h"
+#include "launchers.h"
 
 #define GRU_SPW 4  // stocks per workgroup (= waves)
 
@@ -382,16 +383,7 @@ __global__ __launch_bounds__(512) void gru_bwd_fast_kernel(
 
 extern "C" {
 
-// f32 MFMA recurrence (gru_mfma.hip) — used when H == 64 (exact f32)
-hipError_t fv_gru_fwd_mfma_f32(const float*, const float*, const float*,
-                               float*, float*, float*, float*, int, int, int,
-                               hipStream_t);
-hipError_t fv_gru_bwd_mfma_f32(const float*, const float*, const float*,
-                               const float*, float*, float*, int, int, int,
-                               hipStream_t);
-hipError_t fv_gru_fwd_mfma_f32_infer(const float*, const float*, const float*,
-                                     float*, int, int, int, hipStream_t);
-
+// H == 64 goes to the f32 MFMA recurrence in gru_mfma.hip (exact f32)
 hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
                       float* h_final, float* h_seq, float* h_prev,
                       float* gates4, int N, int T, int H, hipStream_t stream) {

@@ -19,6 +19,7 @@
 // h_prev, gates4=[r,z,n,q] fp32 (+ optional bf16 dgi/dgh copies).
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -692,6 +693,10 @@ hipError_t fv_gru_bwd_mfma_f32(const float* dh_final, const float* h_prev,
   return hipSuccess;
 }
 
+// workgroups of fv_gru_bwd_mfma (GM_S sequences each); with whh_part /
+// bhh_part every one of them writes its own (3H, H) / (3H) wgrad partial
+int fv_gru_wgrad_blocks(int N) { return (N + GM_S - 1) / GM_S; }
+
 hipError_t fv_gru_bwd_mfma(const float* dh_final, const float* h_prev,
                            const float* gates4, const void* whh_bf,
                            float* dgi, float* dgh, void* dgi_bf,
@@ -700,7 +705,7 @@ hipError_t fv_gru_bwd_mfma(const float* dh_final, const float* h_prev,
                            float* whh_part, float* bhh_part, int N,
                            int T, int H, hipStream_t stream) {
   if (H != 64) return hipErrorInvalidValue;
-  dim3 grid((N + GM_S - 1) / GM_S);
+  dim3 grid(fv_gru_wgrad_blocks(N));
   hipLaunchKernelGGL(gru_bwd_mfma_kernel, grid, dim3(256), 0, stream,
                      dh_final, h_prev, gates4, whh_bf, dgi, dgh,
                      (__bf16*)dgi_bf, (__bf16*)dgh_bf,

@@ -33,6 +33,7 @@
 //   64 KB + 32 KB + 32 KB + 192 B, inside SEG_LDS_MAX of predict.hip.
 
 #include "common.h"
+#include "launchers.h"
 
 #define IC_MAX_N 8192
 #define IC_RED 6

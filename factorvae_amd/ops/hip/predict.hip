@@ -18,6 +18,7 @@
 // batch, on its neighbours, or on whether its h rows were staged in LDS.
 
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------
 // LDS map of attn_seg_fwd_kernel (floats, every carve a multiple of 4):

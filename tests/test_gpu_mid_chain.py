@@ -40,8 +40,9 @@ def assert_bits(new, old, what):
 
 
 def dec_nblk(N):
-    iters = min(8, max(1, (N + 511) // 512))
-    return (N + 4 * iters - 1) // (4 * iters)
+    # decoder.hip owns the block count (test_gpu_binding_checks.py holds it
+    # against literals; NBLK_ROWS below does for the counts used here)
+    return ext.dec_nblk(N)
 
 
 def kl_inputs(K, seed=0):

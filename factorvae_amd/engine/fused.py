@@ -134,6 +134,13 @@ class FusedTrainer:
         # kernel (bit-identical); FV_F32_HEAD=0 restores the three launches
         self._f32_head = (not self.bf16
                           and os.environ.get("FV_F32_HEAD", "1") != "0")
+        # every dtype: the fp32 gemm_nn / gemm_tn kernels with the waits taken
+        # out of their loops (variant=1 of the bindings) and, in the default
+        # fp32 tail, the LayerNorm parameter gradients out of the dxln GEMM's
+        # epilogue plus one reduce for the three weight gradients
+        # (bit-identical); FV_F32_GEMM=0 restores the original kernels and
+        # launch sequence
+        self._gv = 0 if os.environ.get("FV_F32_GEMM", "1") == "0" else 1
         # every dtype: the latency-oriented attn_fused_fwd / attn_fused_bwd /
         # enc_fused_fwd kernels (bit-identical); FV_MID=0 restores the
         # original kernels
@@ -631,7 +638,7 @@ class FusedTrainer:
                 ext.attn_softmax_fwd(w["s_att"], mask, w["a_att"], w["sd"],
                                      w["guard"], keep_inv)
                 ext.gemm_tn(w["a_att"], w["h"], w["u"], w["tn_part_u"], 2,
-                            False)
+                            False, variant=self._gv)
                 ext.attn_ctx_fwd(w["u"], self.p_Wv, self.p_bv, w["guard"],
                                  w["ctx"])
                 ext.pred_mlp_fwd(w["ctx"], p("Wl"), p("bl"), p("wmu_p"),
@@ -786,7 +793,8 @@ class FusedTrainer:
                                w["fsig_c"], w["pmu"], w["psig_c"], 1.0)
             e_join = torch.cuda.Event()
             e_join.record(s_att)
-            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"))
+            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"),
+                        variant=self._gv)
         # encoder backward, again enqueued before the side work: every
         # workgroup sums the decoder's factor partials and adds the KL
         # gradients itself
@@ -809,13 +817,13 @@ class FusedTrainer:
             ext.dec_bwd_reduce_heads(w["dec_part"], g("wmu_d"), g("bmu_d"),
                                      g("wsig_d"), g("bsig_d"), N, self.K)
             ext.gemm_tn(w["dz1"], w["h"], g("W1d"), w["tn_part_s"], 2, False,
-                        g("b1d"), w["tn_partb_s"])
+                        g("b1d"), w["tn_partb_s"], variant=self._gv)
             ext.gemm_tn(w["dbeta"], w["h"], g("Wb"), w["tn_part_s"], 2, False,
-                        g("bb"), w["tn_partb_s"])
+                        g("bb"), w["tn_partb_s"], variant=self._gv)
             ext.loss_scalars(w["recon"], yv, w["fmu"], w["fsig_c"], w["pmu"],
                              w["psig_c"], w["loss"], w["mse"], w["kl"])
             ext.gemm_tn(w["dscores"], w["h"], g("Wenc"), w["tn_part_s"], 2,
-                        False, g("benc"), w["tn_partb_s"])
+                        False, g("benc"), w["tn_partb_s"], variant=self._gv)
         return e_join
 
     def _launch_mid_old(self, N, yv, mask, alpha, keep_inv, gatt):
@@ -845,7 +853,7 @@ class FusedTrainer:
                                  g("wmu_p"), g("bmu_p"), g("wsig_p"),
                                  g("bsig_p"))
                 ext.gemm_nn(w["dz2"], p("Wl"), None, w["dctx"], 1.0, False,
-                            False)
+                            False, variant=self._gv)
                 ext.attn_head_bwd(w["dctx"], w["u"], self.p_Wv, w["guard"],
                                   w["du"], gWv, gbv)
                 ext.gemm_nt(w["h"], w["du"], None, w["da"], 1.0, False,
@@ -854,11 +862,12 @@ class FusedTrainer:
                                      w["guard"], w["ds"], w["dc"], keep_inv,
                                      alpha)
                 ext.gemm_tn(w["ds"], w["h"], w["dqk"], w["tn_part_a"], 2,
-                            False)
+                            False, variant=self._gv)
                 ext.attn_qk_bwd(w["dqk"], w["dc"], self.p_q, self.p_Wk,
                                 self.p_bk, gq, gWk, gbk)
             # cross-head Wl wgrad (dz2 is final in both branches)
-            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"))
+            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"),
+                        variant=self._gv)
 
         # ---- decoder backward (main)
         ext.dec_bwd(w["drecon"], w["h"], w["a1"], w["beta"], w["asig_pre"],
@@ -869,9 +878,9 @@ class FusedTrainer:
         fork()
         with _on_side(self):
             ext.gemm_tn(w["dz1"], w["h"], g("W1d"), w["tn_part_s"], 2, False,
-                        g("b1d"), w["tn_partb_s"])
+                        g("b1d"), w["tn_partb_s"], variant=self._gv)
             ext.gemm_tn(w["dbeta"], w["h"], g("Wb"), w["tn_part_s"], 2, False,
-                        g("bb"), w["tn_partb_s"])
+                        g("bb"), w["tn_partb_s"], variant=self._gv)
 
         # ---- encoder backward (heads + stock-axis softmax bwd, main)
         ext.enc_bwd_fused(w["dfmu"], w["dfsig_c"], w["fsig"], w["fsig_pre"],
@@ -881,7 +890,7 @@ class FusedTrainer:
         fork()
         with _on_side(self):
             ext.gemm_tn(w["dscores"], w["h"], g("Wenc"), w["tn_part_s"], 2,
-                        False, g("benc"), w["tn_partb_s"])
+                        False, g("benc"), w["tn_partb_s"], variant=self._gv)
 
     def _launch_extractor_bwd(self, N, T, x2d, chunks, main, sides,
                               comm_overlap):
@@ -978,56 +987,83 @@ class FusedTrainer:
             # in the captured graph, it stays on gru_bwd's hardware queue
             # (the successor that changes queue starts ~10 us late;
             # profiles/f32_tail.md)
+            # FV_F32_GEMM (level 1 only): the pair and the W1x wgrad leave
+            # their slices to ONE reduce at the end of side 1, and the dxln
+            # GEMM forms ln_bwd_params' partials in its epilogue
+            one_reduce = bool(self._gv) and self._f32_tail != 2
             fork(1)
             ext.gemm_nn(w["dgi"].view(R, 3 * H), p("Wih"), None, w["dzx"],
-                        1.0, False, False, lrelu_bwd_of=w["xp"])
+                        1.0, False, False, lrelu_bwd_of=w["xp"],
+                        variant=self._gv)
             with _on_side(self, 1):
                 ext.gemm_tn_pair(w["dgh"].view(R, 3 * H),
                                  w["h_prev"].view(R, H), g("Whh"),
                                  w["dgi"].view(R, 3 * H), w["xp"], g("Wih"),
                                  w["tn_part"], w["tn_part2"], chunks, False,
                                  g("bhh"), g("bih"), w["tn_partb"],
-                                 w["tn_partb2"])
+                                 w["tn_partb2"],
+                                 variant=self._gv, reduce=not one_reduce)
             if self._f32_tail == 2:
                 # opt-in: W1x/LayerNorm gradients straight from
                 # dzx^T @ xhat (no dxln GEMM, no ln_bwd_params pass);
                 # equal to the default only up to fp32 rounding
                 nz = ext.gemm_tn_xhat(w["dzx"], x2d, w["mean"], w["rstd"],
-                                      w["tn_part3"], w["tn_partb3"])
+                                      w["tn_part3"], w["tn_partb3"],
+                                      variant=self._gv)
                 ext.ln_w1x_finish(w["tn_part3"], w["tn_partb3"], nz,
                                   p("W1x"), p("ln_g"), p("ln_b"), g("W1x"),
                                   g("b1x"), g("ln_g"), g("ln_b"))
             else:
-                # the old kernels (bit-identical gradients): the W1x
-                # wgrad follows the pair on side 1 (a third concurrent
-                # branch got serialized BEHIND it on the same hardware
-                # queue: pair last, step 4 % slower), the dxln GEMM and
-                # the LayerNorm parameter gradients stay on main's queue
+                # bit-identical gradients: the W1x wgrad follows the pair
+                # on side 1 (a third concurrent branch got serialized
+                # BEHIND it on the same hardware queue: pair last, step
+                # 4 % slower), the dxln GEMM and the LayerNorm parameter
+                # gradients stay on main's queue
                 fork(1)
-                ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False,
-                            False)
+                ln_fused = bool(self._gv) and ext.gemm_nn_ln(
+                    w["dzx"], p("W1x"), x2d, w["mean"], w["rstd"],
+                    w["ln_part"])
+                if not ln_fused:
+                    # FV_F32_GEMM=0, or ln_bwd_params' row chunks are not
+                    # the GEMM's 64-row tiles at this R
+                    ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0,
+                                False, False, variant=self._gv)
                 with _on_side(self, 1):
                     ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"],
-                                chunks, False, g("b1x"), w["tn_partb3"])
-                ext.ln_bwd_params(x2d, w["dxln"], w["mean"], w["rstd"],
-                                  w["ln_part"], g("ln_g"), g("ln_b"), chunks)
+                                chunks, False, g("b1x"), w["tn_partb3"],
+                                variant=self._gv, reduce=not one_reduce)
+                    if one_reduce:
+                        ext.tn_reduce_list(
+                            [g("Whh"), g("Wih"), g("W1x")],
+                            [w["tn_part"], w["tn_part2"], w["tn_part3"]],
+                            [g("bhh"), g("bih"), g("b1x")],
+                            [w["tn_partb"], w["tn_partb2"], w["tn_partb3"]],
+                            R, chunks, False)
+                if ln_fused:
+                    ext.ln_bwd_reduce(w["ln_part"], g("ln_g"), g("ln_b"), R,
+                                      self.C)
+                else:
+                    ext.ln_bwd_params(x2d, w["dxln"], w["mean"], w["rstd"],
+                                      w["ln_part"], g("ln_g"), g("ln_b"),
+                                      chunks)
         else:
             fork(1)
             with _on_side(self, 1):
                 ext.gemm_tn(w["dgh"].view(R, 3 * H), w["h_prev"].view(R, H),
                             g("Whh"), w["tn_part"], chunks, False,
-                            g("bhh"), w["tn_partb"])
+                            g("bhh"), w["tn_partb"], variant=self._gv)
                 ext.gemm_tn(w["dgi"].view(R, 3 * H), w["xp"], g("Wih"),
                             w["tn_part2"], chunks, False, g("bih"),
-                            w["tn_partb2"])
+                            w["tn_partb2"], variant=self._gv)
             ext.gemm_nn(w["dgi"].view(R, 3 * H), p("Wih"), None, w["dxp"], 1.0,
-                        False, False)
+                        False, False, variant=self._gv)
             ext.lrelu_bwd(w["dxp"], w["xp"], w["dzx"])
             fork(1)
             with _on_side(self, 1):
                 ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"], chunks,
-                            False, g("b1x"), w["tn_partb3"])
-            ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False, False)
+                            False, g("b1x"), w["tn_partb3"], variant=self._gv)
+            ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False, False,
+                        variant=self._gv)
         if not self._f32_tail:
             fork()
             with _on_side(self):

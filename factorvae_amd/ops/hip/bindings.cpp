@@ -122,10 +122,13 @@ void gemm_nt(Tensor A, Tensor W, OptTensor bias, Tensor out, double alpha,
 
 // optional epilogue: out *= lrelu'(Y), Y = lrelu_bwd_of the post-activation
 // (R,Co)
+// variant 0: the original kernel; 1: the pipelined one (bit-identical)
 void gemm_nn(Tensor A, Tensor B, OptTensor bias, Tensor out, double alpha,
              bool accumulate, bool act_lrelu,
-             OptTensor lrelu_bwd_of = c10::nullopt) {
+             OptTensor lrelu_bwd_of = c10::nullopt, long variant = 1) {
   OP("gemm_nn", A);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             " is not 0 or 1");
   const long R = DIM(A, 0), Ci = DIM(A, 1), Co = DIM(B, 1);
   op.require(DIM(B, 0) == Ci && DIM(out, 0) == R && DIM(out, 1) == Co,
              "want A (R,Ci), B (Ci,Co), out (R,Co)");
@@ -135,12 +138,42 @@ void gemm_nn(Tensor A, Tensor B, OptTensor bias, Tensor out, double alpha,
              "lrelu_bwd_of must be (R,Co)");
   RUN(fv_gemm_nn(P_F32(A, R * Ci), P_F32(B, Ci * Co), P_F32(bias, Co),
                  P_F32(out, R * Co), R, Ci, Co, (float)alpha, accumulate,
-                 act_lrelu, P_F32(lrelu_bwd_of, R * Co), cur_stream()));
+                 act_lrelu, P_F32(lrelu_bwd_of, R * Co), (int)variant,
+                 cur_stream()));
 }
 
+// The LayerNorm parameter-gradient partials of dxln = A (R,Ci) @ B (Ci,C)
+// straight from the GEMM (dxln is never stored): part receives what
+// ln_bwd_params' first kernel writes, ln_bwd_reduce finishes. Returns
+// false, with nothing launched, where ln_bwd_params does not work on
+// 64-row blocks; the caller then runs gemm_nn and ln_bwd_params.
+bool gemm_nn_ln(Tensor A, Tensor B, Tensor x, Tensor mean, Tensor rstd,
+                Tensor part) {
+  OP("gemm_nn_ln", A);
+  const long R = DIM(A, 0), Ci = DIM(A, 1), C = DIM(B, 1);
+  op.require(DIM(B, 0) == Ci, "want A (R,Ci), B (Ci,C)");
+  op.require(C >= 1, "B has no columns");
+  const long yblocks = fv_ln_bwd_yblocks(R, C);
+  int ran = 0;
+  RUN(fv_gemm_nn_ln(P_F32(A, R * Ci), P_F32(B, Ci * C), P_F32(x, R * C),
+                    P_F32(mean, R), P_F32(rstd, R),
+                    P_F32(part, yblocks * 2 * C), R, Ci, C, 1.0f, &ran,
+                    cur_stream()));
+  return ran != 0;
+}
+
+// variant 0: the original loop; 1: the pipelined one (bit-identical).
+// reduce = false: a sliced call leaves its slices in part/db_part for
+// tn_reduce_list (part, and db_part with db, are then required).
 void gemm_tn(Tensor A, Tensor B, Tensor out, OptTensor part, long r_chunks,
-             bool accumulate, OptTensor db, OptTensor db_part) {
+             bool accumulate, OptTensor db, OptTensor db_part, long variant,
+             bool reduce) {
   OP("gemm_tn", A);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             " is not 0 or 1");
+  op.require(reduce || (part.has_value() &&
+                        (!db.has_value() || db_part.has_value())),
+             "reduce = false needs part, and db_part with db");
   const long R = DIM(A, 0), M = DIM(A, 1), N = DIM(B, 1);
   op.require(DIM(B, 0) == R && DIM(out, 0) == M && DIM(out, 1) == N,
              "want A (R,M), B (R,N), out (M,N)");
@@ -149,7 +182,7 @@ void gemm_tn(Tensor A, Tensor B, Tensor out, OptTensor part, long r_chunks,
   float* dbpp = dbp ? P_F32(db_part, 32 * M) : nullptr;
   RUN(fv_gemm_tn(P_F32(A, R * M), P_F32(B, R * N), P_F32(out, M * N),
                  P_F32(part, 32 * M * N), dbp, dbpp, R, M, N, NUM(r_chunks),
-                 accumulate, cur_stream()));
+                 accumulate, (int)variant, reduce, cur_stream()));
 }
 
 // Two weight gradients over a common R and M in one launch (+ one
@@ -157,8 +190,14 @@ void gemm_tn(Tensor A, Tensor B, Tensor out, OptTensor part, long r_chunks,
 void gemm_tn_pair(Tensor A0, Tensor B0, Tensor out0, Tensor A1, Tensor B1,
                   Tensor out1, OptTensor part0, OptTensor part1,
                   long r_chunks, bool accumulate, OptTensor db0,
-                  OptTensor db1, OptTensor db_part0, OptTensor db_part1) {
+                  OptTensor db1, OptTensor db_part0, OptTensor db_part1,
+                  long variant, bool reduce) {
   OP("gemm_tn_pair", A0);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             " is not 0 or 1");
+  op.require(reduce || (part0.has_value() &&
+                        (!db0.has_value() || db_part0.has_value())),
+             "reduce = false needs part0/part1, and db_part0/1 with db0/1");
   const long R = DIM(A0, 0), M = DIM(A0, 1);
   const long N0 = DIM(B0, 1), N1 = DIM(B1, 1);
   op.require(DIM(A1, 0) == R && DIM(A1, 1) == M && DIM(B0, 0) == R &&
@@ -182,20 +221,68 @@ void gemm_tn_pair(Tensor A0, Tensor B0, Tensor out0, Tensor A1, Tensor B1,
                       P_F32(out0, M * N0), pp0, dbp0, dbpp0, N0,
                       P_F32(A1, R * M), P_F32(B1, R * N1),
                       P_F32(out1, M * N1), pp1, dbp1, dbpp1, N1, R, M,
-                      NUM(r_chunks), accumulate, cur_stream()));
+                      NUM(r_chunks), accumulate, (int)variant, reduce,
+                      cur_stream()));
+}
+
+// One reduce launch for up to four sliced weight gradients over a common
+// R (gemm_tn / gemm_tn_pair calls with reduce = false and the same
+// r_chunks): out_i (+)= sum of part_i's slices, db_i likewise from
+// db_part_i where db_i is given. Bit-identical to the reduces those calls
+// would have launched themselves. Returns the slice count; at 1 the GEMMs
+// wrote out/db directly and nothing is launched.
+long tn_reduce_list(std::vector<Tensor> outs, std::vector<Tensor> parts,
+                    std::vector<OptTensor> dbs,
+                    std::vector<OptTensor> db_parts, long R, long r_chunks,
+                    bool accumulate) {
+  TORCH_CHECK(!outs.empty(), "tn_reduce_list: outs is empty");
+  OP("tn_reduce_list", outs[0]);
+  const size_t n = outs.size();
+  op.require(n <= 4, "at most 4 problems, got ", n);
+  op.require(parts.size() == n && dbs.size() == n && db_parts.size() == n,
+             "outs, parts, dbs and db_parts must have one entry per problem");
+  NUM(R);
+  const long z = r_chunks > 1 ? fv_tn_xhat_slices((int)R) : 1;
+  const float* part[4];
+  float* out[4];
+  const float* db_part[4];
+  float* db[4];
+  int M[4], N[4];
+  for (size_t i = 0; i < n; ++i) {
+    const long Mi = op.dim(outs[i], "outs[i]", 0);
+    const long Ni = op.dim(outs[i], "outs[i]", 1);
+    M[i] = (int)Mi;
+    N[i] = (int)Ni;
+    out[i] = op.ptr<float>(outs[i], "outs[i]", torch::kFloat32, Mi * Ni,
+                           false);
+    part[i] = op.ptr<float>(parts[i], "parts[i]", torch::kFloat32,
+                            z * Mi * Ni, false);
+    db[i] = op.ptr<float>(dbs[i], "dbs[i]", torch::kFloat32, Mi, true);
+    op.require(!db[i] || db_parts[i].has_value(),
+               "dbs[i] needs db_parts[i]");
+    db_part[i] = db[i] ? op.ptr<float>(db_parts[i], "db_parts[i]",
+                                       torch::kFloat32, z * Mi, false)
+                       : nullptr;
+  }
+  RUN(fv_tn_reduce_list((int)n, part, out, db_part, db, M, N, (int)z,
+                        accumulate, cur_stream()));
+  return z;
 }
 
 // part[z](M,N) = A[slice z]^T @ ((x - mean) * rstd)[slice z],
 // db_part[z](M) = colsum(A[slice z]); returns the slice count z.
 long gemm_tn_xhat(Tensor A, Tensor x, Tensor mean, Tensor rstd, Tensor part,
-                  Tensor db_part) {
+                  Tensor db_part, long variant) {
   OP("gemm_tn_xhat", A);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             " is not 0 or 1");
   const long R = DIM(A, 0), M = DIM(A, 1), N = DIM(x, 1);
   op.require(DIM(x, 0) == R, "want A (R,M), x (R,N)");
   const long nz = fv_tn_xhat_slices(R);
   RUN(fv_gemm_tn_xhat(P_F32(A, R * M), P_F32(x, R * N), P_F32_EQ(mean, R),
                       P_F32_EQ(rstd, R), P_F32(part, nz * M * N),
-                      P_F32(db_part, nz * M), R, M, N, cur_stream()));
+                      P_F32(db_part, nz * M), R, M, N, (int)variant,
+                      cur_stream()));
   return nz;
 }
 
@@ -396,6 +483,17 @@ void ln_bwd_params(Tensor x, Tensor dxln, Tensor mean, Tensor rstd,
                        P_F32(rstd, R), P_F32(part, yblocks * 2 * C),
                        P_F32_EQ(dgamma, C), P_F32_EQ(dbeta, C), R, C,
                        NUM(r_chunks), cur_stream()));
+}
+
+// ln_bwd_params' second kernel alone: dgamma, dbeta from the partials that
+// gemm_nn_ln wrote for R rows of C columns
+void ln_bwd_reduce(Tensor part, Tensor dgamma, Tensor dbeta, long R, long C) {
+  OP("ln_bwd_reduce", part);
+  op.require(R >= 1 && C >= 1, "R = ", R, ", C = ", C, " must be positive");
+  NUM(C);
+  const long yblocks = fv_ln_bwd_yblocks(R, (int)C);
+  RUN(fv_ln_bwd_reduce(P_F32(part, yblocks * 2 * C), P_F32_EQ(dgamma, C),
+                       P_F32_EQ(dbeta, C), R, (int)C, cur_stream()));
 }
 
 // ----------------------------------------------------------------- fp8
@@ -1073,18 +1171,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_nt", &gemm_nt);
   mod.def("gemm_nn", &gemm_nn, py::arg("A"), py::arg("B"), py::arg("bias"),
           py::arg("out"), py::arg("alpha"), py::arg("accumulate"),
-          py::arg("act_lrelu"), py::arg("lrelu_bwd_of") = py::none());
+          py::arg("act_lrelu"), py::arg("lrelu_bwd_of") = py::none(),
+          py::arg("variant") = 1);
+  mod.def("gemm_nn_ln", &gemm_nn_ln);
+  mod.def("ln_bwd_reduce", &ln_bwd_reduce);
+  mod.def("tn_reduce_list", &tn_reduce_list, py::arg("outs"),
+          py::arg("parts"), py::arg("dbs"), py::arg("db_parts"), py::arg("R"),
+          py::arg("r_chunks"), py::arg("accumulate"));
   mod.def("gemm_tn_pair", &gemm_tn_pair, py::arg("A0"), py::arg("B0"),
           py::arg("out0"), py::arg("A1"), py::arg("B1"), py::arg("out1"),
           py::arg("part0"), py::arg("part1"), py::arg("r_chunks"),
           py::arg("accumulate"), py::arg("db0") = py::none(),
           py::arg("db1") = py::none(), py::arg("db_part0") = py::none(),
-          py::arg("db_part1") = py::none());
-  mod.def("gemm_tn_xhat", &gemm_tn_xhat);
+          py::arg("db_part1") = py::none(), py::arg("variant") = 1,
+          py::arg("reduce") = true);
+  mod.def("gemm_tn_xhat", &gemm_tn_xhat, py::arg("A"), py::arg("x"),
+          py::arg("mean"), py::arg("rstd"), py::arg("part"),
+          py::arg("db_part"), py::arg("variant") = 1);
   mod.def("ln_w1x_finish", &ln_w1x_finish);
   mod.def("gemm_tn", &gemm_tn, py::arg("A"), py::arg("B"), py::arg("out"),
           py::arg("part"), py::arg("r_chunks"), py::arg("accumulate"),
-          py::arg("db") = py::none(), py::arg("db_part") = py::none());
+          py::arg("db") = py::none(), py::arg("db_part") = py::none(),
+          py::arg("variant") = 1, py::arg("reduce") = true);
   mod.def("colsum", &colsum);
   mod.def("gemm_nt_bf16", &gemm_nt_bf16, py::arg("A"), py::arg("W"),
           py::arg("bias"), py::arg("out_f32"), py::arg("out_bf16"),

@@ -661,6 +661,23 @@ int fv_ln_bwd_yblocks(long R, int C) {
   return (int)ln_bwd_geometry(R, C, &rpb);
 }
 
+int fv_ln_bwd_rows(long R, int C) {
+  long rpb;
+  ln_bwd_geometry(R, C, &rpb);
+  return (int)rpb;
+}
+
+hipError_t fv_ln_bwd_reduce(const float* part, float* dgamma, float* dbeta,
+                            long R, int C, hipStream_t stream) {
+  long rpb;
+  const unsigned yblocks = ln_bwd_geometry(R, C, &rpb);
+  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * C + 3) / 4),
+                     dim3(256), 0, stream, part, dgamma, dbeta,
+                     (int)yblocks, C);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
 hipError_t fv_ln_bwd_params(const float* x, const float* dxln,
                             const float* mean, const float* rstd,
                             float* part, float* dgamma, float* dbeta,

@@ -13,6 +13,12 @@
 //   gemm_tn_xhat + ln_w1x_finish: W1x/b1x/LayerNorm gradients from
 //             dzx^T @ xhat slices (no dxln; docs/KERNELS.md)
 //   colsum:   out(C)    (+)= sum_r A(R,C)         (bias grads)
+// gemm_nn and the gemm_tn family each have a second, pipelined kernel
+// (variant 1 of the launchers, bit-identical; docs/KERNELS.md, "The fp32
+// GEMM mainloops"); gemm_nn_ln is the pipelined gemm_nn with ln_bwd_params'
+// loop as its epilogue, tn_reduce_list one reduce for several gemm_tn calls.
+
+#include <type_traits>
 
 #include "common.h"
 #include "launchers.h"
@@ -222,6 +228,243 @@ __global__ __launch_bounds__(256) void gemm_nn_kernel(
   }
 }
 
+// gemm_nn with the waits taken out of its loops (variant >= 1 of
+// fv_gemm_nn; docs/KERNELS.md, profiles/f32_gemm.md). Same tiles, same
+// LDS image, same MFMA order per accumulator as gemm_nn_kernel, so every
+// output is bit-identical; what changes is when things are waited for:
+//  - global loads are branch-free (addresses clamped into range, padding
+//    zeros selected at the LDS store) and run D k-tiles ahead through a ring
+//    of D register sets, so the wait before an LDS store is a counted one
+//    for the oldest set only;
+//  - the fragments of k-groups 2p+2, 2p+3 are read from LDS before the
+//    MFMAs of groups 2p, 2p+1 issue (eh_mma_ktile's scheme);
+//  - everything the epilogue reads from memory is loaded before the last
+//    k-tile's MFMAs, so the epilogue only computes and stores.
+// LN: the 64x64 result tile goes to LDS instead of `out` and the workgroup
+// runs ln_bwd_params_kernel's loop on it (64 rows per block: the launcher
+// checks the geometry), writing that kernel's partials; dxln is never
+// stored. Needs R, Ci, Co >= 1 (the clamps).
+template <int D, bool LN>
+__global__ __launch_bounds__(256) void gemm_nn_pipe_kernel(
+    const float* __restrict__ A, const float* __restrict__ B,
+    const float* __restrict__ bias, const float* __restrict__ Y,
+    float* __restrict__ out, const float* __restrict__ lx,
+    const float* __restrict__ lmean, const float* __restrict__ lrstd,
+    float* __restrict__ lpart, int R, int Ci, int Co, float alpha,
+    int flags) {
+  // row strides 34 and 80: a 32-lane read group (16 fi x 2 fk) then touches
+  // 32 different banks (2 fi + fk, 16 fk + fi); with 33 and 65 every read
+  // was a 2-way conflict
+  __shared__ float As[2][BR][BK + 2];
+  __shared__ float Bs[2][BK][BC + 16];
+
+  const int r0 = blockIdx.y * BR;
+  const int c0 = blockIdx.x * BC;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int fi = lane & 15;
+  const int fk = lane >> 4;
+
+  const int s_row0 = tid >> 5;
+  const int s_k = tid & 31;
+  const int b_k0 = tid >> 6;
+  const int b_c = tid & 63;
+
+  f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+
+  const int ktiles = (Ci + BK - 1) / BK;
+  const int last = ktiles - 1;
+  float pa[D][8], pb[D][8];
+  // tile t may lie past the last one: its loads are clamped duplicates
+  // that are never stored
+  auto stage_regs = [&](float (&qa)[8], float (&qb)[8], int t) {
+    const int k0 = t * BK;
+    const int gk = min(k0 + s_k, Ci - 1);
+    const int bc = min(c0 + b_c, Co - 1);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int row = min(r0 + s_row0 + 8 * u, R - 1);
+      qa[u] = A[(long)row * Ci + gk];
+      const int bk = min(k0 + b_k0 + 4 * u, Ci - 1);
+      qb[u] = B[(long)bk * Co + bc];
+    }
+  };
+  auto regs_to_lds = [&](const float (&qa)[8], const float (&qb)[8], int t,
+                         int buf) {
+    const int k0 = t * BK;
+    const bool ka = k0 + s_k < Ci;
+    const bool cb = c0 + b_c < Co;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const bool oa = ka && (r0 + s_row0 + 8 * u < R);
+      const bool ob = cb && (k0 + b_k0 + 4 * u < Ci);
+      As[buf][s_row0 + 8 * u][s_k] = oa ? qa[u] : 0.0f;
+      Bs[buf][b_k0 + 4 * u][b_c] = ob ? qb[u] : 0.0f;
+    }
+  };
+  auto mma_tile = [&](int buf) {
+    float a[2][2], b[2][4][2];
+    auto frag = [&](int set, int kk) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        a[set][h] = As[buf][wv * 16 + fi][kk + 4 * h + fk];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+          b[set][jt][h] = Bs[buf][kk + 4 * h + fk][jt * 16 + fi];
+      }
+    };
+    frag(0, 0);
+#pragma unroll
+    for (int p = 0; p < BK / 8; ++p) {
+      if (p + 1 < BK / 8) frag((p + 1) & 1, (p + 1) * 8);
+      __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMAs
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+          acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              a[p & 1][h], b[p & 1][jt][h], acc[jt], 0, 0, 0);
+      }
+    }
+  };
+
+  // the sets are loaded in ring order, oldest first (the scheduler would
+  // mix them, and the loop's counted waits rely on the order)
+  stage_regs(pa[0], pb[0], 0);
+  __builtin_amdgcn_sched_barrier(0);
+  regs_to_lds(pa[0], pb[0], 0, 0);
+#pragma unroll
+  for (int d = 1; d < D; ++d) {
+    stage_regs(pa[d], pb[d], d);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // step kt < last: set kt % D is free (tile kt is in LDS) and takes tile
+  // kt + D; set (kt + 1) % D holds tile kt + 1, the oldest in flight.
+  // Whole groups of D steps run in a loop without a branch in its body: a
+  // path that skipped a step's loads would, where it joins, turn the
+  // counted waits of the later steps into nearly full ones.
+  int kt = 0;
+  for (; kt + D <= last; kt += D) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      __syncthreads();
+      stage_regs(pa[d], pb[d], kt + d + D);
+      mma_tile((kt + d) & 1);
+      __syncthreads();
+      regs_to_lds(pa[(d + 1) % D], pb[(d + 1) % D], kt + d + 1,
+                  1 - ((kt + d) & 1));
+    }
+  }
+  // the last - kt < D steps left load nothing: their tiles are in flight
+  // in sets 1, 2, ... (nested, so that no step is entered from two sides)
+  auto rest = [&](auto self, auto rc) {
+    constexpr int r = decltype(rc)::value;
+    if constexpr (r < D - 1) {
+      if (kt + r < last) {
+        __syncthreads();
+        mma_tile((kt + r) & 1);
+        __syncthreads();
+        regs_to_lds(pa[r + 1], pb[r + 1], kt + r + 1, 1 - ((kt + r) & 1));
+        self(self, std::integral_constant<int, r + 1>{});
+      }
+    }
+  };
+  rest(rest, std::integral_constant<int, 0>{});
+
+  // the last k-tile, with the epilogue's operands loaded under its MFMAs
+  __syncthreads();
+  float ey[16], eo[16], eb[4], ex[16], emu[16], ers[16];
+  if (LN) {
+    const int c = min(c0 + lane, Co - 1);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int r = min(r0 + wv + 4 * i, R - 1);
+      ex[i] = lx[(long)r * Co + c];
+      emu[i] = lmean[r];
+      ers[i] = lrstd[r];
+    }
+  } else {
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) {
+      const int gc = min(c0 + jt * 16 + fi, Co - 1);
+      eb[jt] = 0.0f;
+      if (flags & 4) eb[jt] = bias[gc];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int gr = min(r0 + wv * 16 + fk * 4 + rr, R - 1);
+        ey[jt * 4 + rr] = 0.0f;
+        eo[jt * 4 + rr] = 0.0f;
+        if (flags & 8) ey[jt * 4 + rr] = Y[(long)gr * Co + gc];
+        if (flags & 1) eo[jt * 4 + rr] = out[(long)gr * Co + gc];
+      }
+    }
+  }
+  mma_tile(last & 1);
+
+  if (LN) {
+    // 64 x 65 floats fit in As (2 x 64 x 34)
+    float(*Ts)[BC + 1] = reinterpret_cast<float(*)[BC + 1]>(&As[0][0][0]);
+    float(*pg)[64] = reinterpret_cast<float(*)[64]>(&Bs[0][0][0]);
+    float(*pbs)[64] = pg + 4;
+    __syncthreads();  // every wave is done with the last tile's fragments
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        float v = acc[jt][rr];
+        v *= alpha;
+        Ts[wv * 16 + fk * 4 + rr][jt * 16 + fi] = v;
+      }
+    }
+    __syncthreads();
+    // ln_bwd_params_kernel's loop: wave wv walks rows wv, wv+4, ... of the
+    // block's 64, lane = column
+    float dg = 0.0f, db = 0.0f;
+    if (c0 + lane < Co) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        if (r0 + wv + 4 * i < R) {
+          const float g = Ts[wv + 4 * i][lane];
+          const float xh = (ex[i] - emu[i]) * ers[i];
+          dg = fmaf(g, xh, dg);
+          db += g;
+        }
+      }
+    }
+    pg[wv][lane] = dg;
+    pbs[wv][lane] = db;
+    __syncthreads();
+    if (wv == 0 && c0 + lane < Co) {
+      const int c = c0 + lane;
+      lpart[(long)c * gridDim.y + blockIdx.y] =
+          pg[0][lane] + pg[1][lane] + pg[2][lane] + pg[3][lane];
+      lpart[((long)Co + c) * gridDim.y + blockIdx.y] =
+          pbs[0][lane] + pbs[1][lane] + pbs[2][lane] + pbs[3][lane];
+    }
+    return;
+  }
+
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt) {
+    const int gc = c0 + jt * 16 + fi;
+    if (gc >= Co) continue;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int gr = r0 + wv * 16 + fk * 4 + rr;
+      if (gr >= R) continue;
+      float v = acc[jt][rr];
+      if (flags & 4) v += eb[jt];
+      v *= alpha;
+      if (flags & 2) v = lrelu_(v);
+      if (flags & 8) v *= lrelu_grad_from_out_(ey[jt * 4 + rr]);
+      if (flags & 1) v += eo[jt * 4 + rr];
+      out[(long)gr * Co + gc] = v;
+    }
+  }
+}
+
 // out(M,N) (+)= A(R,M)^T @ B(R,N); R-chunked over gridDim.z.
 // gridDim.z == 1: plain write to out. gridDim.z > 1: each z-slice writes
 // its partial tile to part[z][M][N] (plain stores); tn_reduce_kernel then
@@ -368,14 +611,205 @@ __device__ __forceinline__ void gemm_tn_body(
   }
 }
 
+// gemm_tn_body with its prefetch left in flight (variant >= 1 of the three
+// launchers; docs/KERNELS.md, profiles/f32_gemm.md). Same slices, same
+// tiles, same LDS image and the same ascending MFMA chain per accumulator,
+// so out, part, db and db_part are bit-identical. The differences:
+//  - global loads are branch-free (clamped addresses; the zeros of rows
+//    past the slice and columns past M/N are selected at the LDS store) and
+//    run D 32-row tiles ahead through a ring of D register sets;
+//  - bsum is formed where the staged registers are consumed, at the LDS
+//    store after the tile's MFMAs (same pa[u] values, same u and tile
+//    order), so nothing waits for the loads above the MFMAs;
+//  - the tile's eight fragment pairs are read from LDS ahead of the MFMA
+//    chain, which then runs on counted waits.
+template <bool XHAT, int D>
+__device__ __forceinline__ void gemm_tn_pipe_body(
+    const float* __restrict__ A, const float* __restrict__ B,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ out, float* __restrict__ part,
+    float* __restrict__ db, float* __restrict__ db_part,
+    int R, int M, int N, int accumulate, int bx, int by, int bz, int nz) {
+  // row stride 48: a 32-lane read group (16 fi x 2 fk) touches 32 different
+  // banks (16 fk + fi); with 33 every read was a 2-way conflict
+  __shared__ float As[2][TKR][TM + 16];
+  __shared__ float Bs[2][TKR][TN_ + 16];
+
+  const int m0 = bx * TM;
+  const int n0 = by * TN_;
+  const int chunk = (R + nz - 1) / nz;
+  const int rbeg = bz * chunk;
+  const int rend = min(rbeg + chunk, R);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int fi = lane & 15;
+  const int fk = lane >> 4;
+  const int mt = (wv & 1) * 16;
+  const int nt = (wv >> 1) * 16;
+
+  const bool do_bias = (db != nullptr || (XHAT && db_part != nullptr)) &&
+                       (by == 0);
+  float bsum = 0.0f;
+
+  f32x4 acc = {0, 0, 0, 0};
+
+  const int s_kr0 = tid >> 5;
+  const int s_c = tid & 31;
+  const int ktiles = (rend - rbeg + TKR - 1) / TKR;
+  const bool ca = m0 + s_c < M;
+  const bool cb = n0 + s_c < N;
+  const int ga = min(m0 + s_c, M - 1);
+  const int gb = min(n0 + s_c, N - 1);
+  float pa[D][4], pb[D][4], pmu[D][4], prs[D][4];
+  // tile t may lie past the slice: its loads are clamped duplicates of the
+  // slice's last row and are never stored (ktiles > 0, so rend > rbeg)
+  auto stage_regs = [&](int s, int t) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int gr = min(rbeg + t * TKR + s_kr0 + 8 * u, rend - 1);
+      pa[s][u] = A[(long)gr * M + ga];
+      pb[s][u] = B[(long)gr * N + gb];
+      if (XHAT) {
+        pmu[s][u] = mean[gr];
+        prs[s][u] = rstd[gr];
+      }
+    }
+  };
+  auto regs_to_lds = [&](int s, int t, int buf) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool rok = rbeg + t * TKR + s_kr0 + 8 * u < rend;
+      const float av = (rok && ca) ? pa[s][u] : 0.0f;
+      const float bv = XHAT ? (pb[s][u] - pmu[s][u]) * prs[s][u] : pb[s][u];
+      if (do_bias) bsum += av;
+      As[buf][s_kr0 + 8 * u][s_c] = av;
+      Bs[buf][s_kr0 + 8 * u][s_c] = (rok && cb) ? bv : 0.0f;
+    }
+  };
+
+  if (ktiles > 0) {
+    // the sets are loaded in ring order, oldest first (the scheduler would
+    // mix them, and the loop's counted waits rely on the order)
+    stage_regs(0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    regs_to_lds(0, 0, 0);
+#pragma unroll
+    for (int d = 1; d < D; ++d) {
+      stage_regs(d, d);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  auto mma_tile = [&](int buf) {
+    float fa[TKR / 4], fb[TKR / 4];
+#pragma unroll
+    for (int q = 0; q < TKR / 4; ++q) {
+      fa[q] = As[buf][4 * q + fk][mt + fi];
+      fb[q] = Bs[buf][4 * q + fk][nt + fi];
+    }
+    __builtin_amdgcn_sched_barrier(0);  // reads and loads stay above
+#pragma unroll
+    for (int q = 0; q < TKR / 4; ++q)
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[q], fb[q], acc, 0, 0, 0);
+  };
+  // step kt < last: set kt % D is free (tile kt is in LDS) and takes tile
+  // kt + D; set (kt + 1) % D holds tile kt + 1, the oldest in flight.
+  // Whole groups of D steps run in a loop without a branch in its body: a
+  // path that skipped a step's loads would, where it joins, turn the
+  // counted waits of the later steps into nearly full ones.
+  if (ktiles > 0) {
+    const int last = ktiles - 1;
+    int kt = 0;
+    for (; kt + D <= last; kt += D) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        __syncthreads();
+        stage_regs(d, kt + d + D);
+        mma_tile((kt + d) & 1);
+        __syncthreads();
+        regs_to_lds((d + 1) % D, kt + d + 1, 1 - ((kt + d) & 1));
+      }
+    }
+    // the last - kt < D steps left load nothing: their tiles are in flight
+    // in sets 1, 2, ... (nested, so that no step is entered from two sides)
+    auto rest = [&](auto self, auto rc) {
+      constexpr int r = decltype(rc)::value;
+      if constexpr (r < D - 1) {
+        if (kt + r < last) {
+          __syncthreads();
+          mma_tile((kt + r) & 1);
+          __syncthreads();
+          regs_to_lds(r + 1, kt + r + 1, 1 - ((kt + r) & 1));
+          self(self, std::integral_constant<int, r + 1>{});
+        }
+      }
+    };
+    rest(rest, std::integral_constant<int, 0>{});
+    __syncthreads();
+    mma_tile(last & 1);
+  }
+
+  const bool direct = !XHAT && (nz == 1);
+  if (do_bias) {
+    __syncthreads();
+    As[0][s_kr0][s_c] = bsum;
+    __syncthreads();
+    if (tid < TM) {
+      float s = 0.0f;
+#pragma unroll
+      for (int gq = 0; gq < 8; ++gq) s += As[0][gq][tid];
+      const int gm = m0 + tid;
+      if (gm < M) {
+        if (direct) {
+          if (accumulate) db[gm] += s; else db[gm] = s;
+        } else {
+          db_part[(long)bz * M + gm] = s;
+        }
+      }
+    }
+  }
+
+  const int gn = n0 + nt + fi;
+  if (gn >= N) return;
+  float* po = direct ? out : part + (long)bz * M * N;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int gm = m0 + mt + (lane >> 4) * 4 + rr;
+    if (gm >= M) continue;
+    float* dst = &po[(long)gm * N + gn];
+    if (direct && accumulate)
+      *dst += acc[rr];
+    else
+      *dst = acc[rr];
+  }
+}
+
+// D = 0: the original body; D >= 1: the pipelined one, D tiles ahead
+template <bool XHAT, int D>
+__device__ __forceinline__ void gemm_tn_sel(
+    const float* __restrict__ A, const float* __restrict__ B,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ out, float* __restrict__ part,
+    float* __restrict__ db, float* __restrict__ db_part,
+    int R, int M, int N, int accumulate, int bx, int by, int bz, int nz) {
+  if constexpr (D == 0)
+    gemm_tn_body<XHAT>(A, B, mean, rstd, out, part, db, db_part, R, M, N,
+                       accumulate, bx, by, bz, nz);
+  else
+    gemm_tn_pipe_body<XHAT, D>(A, B, mean, rstd, out, part, db, db_part, R,
+                               M, N, accumulate, bx, by, bz, nz);
+}
+
+template <int D>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(
     const float* __restrict__ A, const float* __restrict__ B,
     float* __restrict__ out, float* __restrict__ part,
     float* __restrict__ db, float* __restrict__ db_part,
     int R, int M, int N, int accumulate) {
-  gemm_tn_body<false>(A, B, nullptr, nullptr, out, part, db, db_part, R, M, N,
-                      accumulate, blockIdx.x, blockIdx.y, blockIdx.z,
-                      gridDim.z);
+  gemm_tn_sel<false, D>(A, B, nullptr, nullptr, out, part, db, db_part, R, M,
+                        N, accumulate, blockIdx.x, blockIdx.y, blockIdx.z,
+                        gridDim.z);
 }
 
 // Two TN problems with a common R and M in one launch (the GRU's Whh and
@@ -392,29 +826,32 @@ struct TnProblem {
   float* db_part;
   int N;
 };
+template <int D>
 __global__ __launch_bounds__(256) void gemm_tn_pair_kernel(
     TnProblem p0, TnProblem p1, int R, int M, int accumulate) {
   const int mtiles = (M + TM - 1) / TM;
   const int tiles0 = mtiles * ((p0.N + TN_ - 1) / TN_);
   const bool second = (int)blockIdx.x >= tiles0;
   const int tile = second ? (int)blockIdx.x - tiles0 : (int)blockIdx.x;
-  gemm_tn_body<false>(second ? p1.A : p0.A, second ? p1.B : p0.B, nullptr,
-                      nullptr, second ? p1.out : p0.out,
-                      second ? p1.part : p0.part, second ? p1.db : p0.db,
-                      second ? p1.db_part : p0.db_part, R, M,
-                      second ? p1.N : p0.N, accumulate, tile % mtiles,
-                      tile / mtiles, blockIdx.z, gridDim.z);
+  gemm_tn_sel<false, D>(second ? p1.A : p0.A, second ? p1.B : p0.B, nullptr,
+                        nullptr, second ? p1.out : p0.out,
+                        second ? p1.part : p0.part, second ? p1.db : p0.db,
+                        second ? p1.db_part : p0.db_part, R, M,
+                        second ? p1.N : p0.N, accumulate, tile % mtiles,
+                        tile / mtiles, blockIdx.z, gridDim.z);
 }
 
 // part[z](M,N) = A[slice z]^T @ xhat[slice z], db_part[z](M) =
 // colsum(A[slice z]) with xhat = (x - mean) * rstd formed while staging x.
+template <int D>
 __global__ __launch_bounds__(256) void gemm_tn_xhat_kernel(
     const float* __restrict__ A, const float* __restrict__ x,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     float* __restrict__ part, float* __restrict__ db_part,
     int R, int M, int N) {
-  gemm_tn_body<true>(A, x, mean, rstd, nullptr, part, nullptr, db_part, R, M,
-                     N, 0, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z);
+  gemm_tn_sel<true, D>(A, x, mean, rstd, nullptr, part, nullptr, db_part, R,
+                       M, N, 0, blockIdx.x, blockIdx.y, blockIdx.z,
+                       gridDim.z);
 }
 
 // out[e] += sum_z part[z][e]; db[m] += sum_z db_part[z][m] — fixed z
@@ -474,6 +911,48 @@ __global__ __launch_bounds__(256) void tn_reduce_pair_kernel(
                  second ? p1.db_part : p0.db_part, second ? p1.db : p0.db,
                  m_elems, z, accumulate,
                  second ? (int)blockIdx.x - blocks0 : (int)blockIdx.x);
+}
+
+// tn_reduce_pair_kernel for a short list of problems, each with its own M
+// and N: problem 0's blocks, then problem 1's, ... Every element's sum is
+// tn_reduce_body's, i.e. that of the problem's own tn_reduce launch.
+#define TN_LIST_MAX 4
+struct TnReduceItem {
+  const float* part;
+  float* out;
+  const float* db_part;
+  float* db;  // null: no bias gradient
+  int M;
+  int N;
+};
+struct TnReduceList {
+  TnReduceItem it[TN_LIST_MAX];
+  int n;
+};
+static inline long tn_reduce_blocks(const TnReduceItem& q) {
+  return ((long)q.M * q.N + (q.db ? q.M : 0) + 63) / 64;
+}
+__global__ __launch_bounds__(256) void tn_reduce_list_kernel(
+    TnReduceList L, int z, int accumulate) {
+  long block = blockIdx.x;
+  int i = 0;
+  // constant indices and select chains throughout: indexing the by-value
+  // struct with a run-time i could put it in scratch
+#pragma unroll
+  for (int j = 0; j + 1 < TN_LIST_MAX; ++j) {
+    const long nb = ((long)L.it[j].M * L.it[j].N +
+                     (L.it[j].db ? L.it[j].M : 0) + 63) / 64;
+    if (i == j && j + 1 < L.n && block >= nb) {
+      block -= nb;
+      i = j + 1;
+    }
+  }
+  TnReduceItem q = L.it[0];
+#pragma unroll
+  for (int j = 1; j < TN_LIST_MAX; ++j)
+    if (i == j) q = L.it[j];
+  tn_reduce_body(q.part, q.out, (long)q.M * q.N, q.db_part, q.db,
+                 q.db ? q.M : 0, z, accumulate, block);
 }
 
 // Finish of the dxln-free LayerNorm + W1x backward. With
@@ -584,6 +1063,19 @@ __global__ __launch_bounds__(256) void lrelu_bwd_kernel(
   if (idx < total) dZ[idx] = dY[idx] * lrelu_grad_from_out_(Y[idx]);
 }
 
+// variant -> global prefetch distance of the pipelined kernels (0: the
+// original kernel, -1: no such variant). Measured at the benchmark's tail
+// shapes (profiles/f32_gemm.md): gemm_nn 1 and 2 tiles ahead are equal
+// within 3 %, gemm_tn is fastest 2 ahead (4 ahead is slower again).
+#define NN_DIST 1
+#define TN_DIST 2
+static inline int nn_distance(int variant) {
+  return variant == 0 ? 0 : variant == 1 ? NN_DIST : -1;
+}
+static inline int tn_distance(int variant) {
+  return variant == 0 ? 0 : variant == 1 ? TN_DIST : -1;
+}
+
 extern "C" {
 
 hipError_t fv_gemm_nt(const float* A, const float* W, const float* bias,
@@ -600,22 +1092,59 @@ hipError_t fv_gemm_nt(const float* A, const float* W, const float* bias,
 hipError_t fv_gemm_nn(const float* A, const float* B, const float* bias,
                       float* out, int R, int Ci, int Co, float alpha,
                       int accumulate, int act_lrelu, const float* lrelu_bwd_of,
-                      hipStream_t stream) {
+                      int variant, hipStream_t stream) {
+  // variant 0: gemm_nn_kernel; 1: gemm_nn_pipe_kernel (bit-identical)
+  variant = nn_distance(variant);
+  if (variant < 0) return hipErrorInvalidValue;
   int flags = (accumulate ? 1 : 0) | (act_lrelu ? 2 : 0) | (bias ? 4 : 0) |
               (lrelu_bwd_of ? 8 : 0);
   dim3 grid((Co + BC - 1) / BC, (R + BR - 1) / BR);
-  hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream,
-                     A, B, bias, lrelu_bwd_of, out, R, Ci, Co, alpha, flags);
+  if (R < 1 || Ci < 1 || Co < 1) variant = 0;  // the pipe kernel's clamps
+  if (variant)
+    hipLaunchKernelGGL((gemm_nn_pipe_kernel<NN_DIST, false>), grid, dim3(256), 0,
+                       stream, A, B, bias, lrelu_bwd_of, out, nullptr, nullptr,
+                       nullptr, nullptr, R, Ci, Co, alpha, flags);
+  else
+    hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream,
+                       A, B, bias, lrelu_bwd_of, out, R, Ci, Co, alpha, flags);
   HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// LayerNorm parameter-gradient partials straight from the dxln GEMM:
+// part = what fv_ln_bwd_params' first kernel writes for
+// dxln = alpha * (A(R,Ci) @ B(Ci,C)), without storing dxln; follow with
+// fv_ln_bwd_reduce. Valid only where fv_ln_bwd_params works on 64-row
+// blocks, gemm_nn's tile height (fv_ln_bwd_rows); otherwise *ran = 0 and
+// nothing is launched (the caller runs gemm_nn and ln_bwd_params).
+hipError_t fv_gemm_nn_ln(const float* A, const float* B, const float* x,
+                         const float* mean, const float* rstd, float* part,
+                         long R, int Ci, int C, float alpha, int* ran,
+                         hipStream_t stream) {
+  *ran = 0;
+  if (R < 1 || R > 0x7fffffffL || Ci < 1 || C < 1) return hipSuccess;
+  if (fv_ln_bwd_rows(R, C) != BR) return hipSuccess;
+  dim3 grid((C + BC - 1) / BC, (unsigned)((R + BR - 1) / BR));
+  if (grid.y > 65535u) return hipSuccess;
+  hipLaunchKernelGGL((gemm_nn_pipe_kernel<NN_DIST, true>), grid, dim3(256), 0,
+                     stream, A, B, nullptr, nullptr, nullptr, x, mean, rstd,
+                     part, (int)R, Ci, C, alpha, 0);
+  HIP_CHECK_LAST();
+  *ran = 1;
   return hipSuccess;
 }
 
 hipError_t fv_gemm_tn(const float* A, const float* B, float* out,
                       float* part, float* db, float* db_part,
                       int R, int M, int N, int r_chunks,
-                      int accumulate, hipStream_t stream) {
+                      int accumulate, int variant, int reduce,
+                      hipStream_t stream) {
   // r_chunks > 1 is a request to chunk the R-reduction; the launcher
   // picks the actual split (>=512 rows per chunk, <=32 slices).
+  // variant 0: the original loop; 1: the pipelined one (bit-identical).
+  // reduce = 0: leave the slices in part/db_part for fv_tn_reduce_list.
+  variant = tn_distance(variant);
+  if (variant < 0) return hipErrorInvalidValue;
   if (r_chunks < 1) r_chunks = 1;
   if (!part) r_chunks = 1;
   if (r_chunks > 1) {
@@ -625,10 +1154,14 @@ hipError_t fv_gemm_tn(const float* A, const float* B, float* out,
   }
   if (r_chunks > 1 && db && !db_part) r_chunks = 1;  // need partial space
   dim3 grid((M + TM - 1) / TM, (N + TN_ - 1) / TN_, r_chunks);
-  hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, stream,
-                     A, B, out, part, db, db_part, R, M, N, accumulate);
+#define TN_LAUNCH(D)                                                       \
+  hipLaunchKernelGGL(gemm_tn_kernel<D>, grid, dim3(256), 0, stream, A, B, \
+                     out, part, db, db_part, R, M, N, accumulate)
+  if (variant) TN_LAUNCH(TN_DIST);
+  else TN_LAUNCH(0);
+#undef TN_LAUNCH
   HIP_CHECK_LAST();
-  if (r_chunks > 1) {
+  if (r_chunks > 1 && reduce) {
     const long elems = (long)M * N;
     const long m_elems = db ? M : 0;
     dim3 rgrid((unsigned)((elems + m_elems + 63) / 64));
@@ -649,7 +1182,9 @@ hipError_t fv_gemm_tn_pair(const float* A0, const float* B0, float* out0,
                            const float* A1, const float* B1, float* out1,
                            float* part1, float* db1, float* db_part1, int N1,
                            int R, int M, int r_chunks, int accumulate,
-                           hipStream_t stream) {
+                           int variant, int reduce, hipStream_t stream) {
+  variant = tn_distance(variant);
+  if (variant < 0) return hipErrorInvalidValue;
   if (r_chunks < 1) r_chunks = 1;
   if (!part0 || !part1) r_chunks = 1;
   if (r_chunks > 1) {
@@ -662,10 +1197,14 @@ hipError_t fv_gemm_tn_pair(const float* A0, const float* B0, float* out0,
   const TnProblem p1 = {A1, B1, out1, part1, db1, db_part1, N1};
   const int mtiles = (M + TM - 1) / TM;
   const int tiles = mtiles * ((N0 + TN_ - 1) / TN_ + (N1 + TN_ - 1) / TN_);
-  hipLaunchKernelGGL(gemm_tn_pair_kernel, dim3(tiles, 1, r_chunks), dim3(256),
-                     0, stream, p0, p1, R, M, accumulate);
+#define TN_LAUNCH(D)                                                     \
+  hipLaunchKernelGGL(gemm_tn_pair_kernel<D>, dim3(tiles, 1, r_chunks),  \
+                     dim3(256), 0, stream, p0, p1, R, M, accumulate)
+  if (variant) TN_LAUNCH(TN_DIST);
+  else TN_LAUNCH(0);
+#undef TN_LAUNCH
   HIP_CHECK_LAST();
-  if (r_chunks > 1) {
+  if (r_chunks > 1 && reduce) {
     const long m_elems = db0 ? M : 0;
     const long b0 = ((long)M * N0 + m_elems + 63) / 64;
     const long b1 = ((long)M * N1 + m_elems + 63) / 64;
@@ -690,10 +1229,42 @@ int fv_tn_xhat_slices(int R) {
 // colsum(A[slice z]); never reduced here (ln_w1x_finish sums the slices).
 hipError_t fv_gemm_tn_xhat(const float* A, const float* x, const float* mean,
                            const float* rstd, float* part, float* db_part,
-                           int R, int M, int N, hipStream_t stream) {
+                           int R, int M, int N, int variant,
+                           hipStream_t stream) {
+  variant = tn_distance(variant);
+  if (variant < 0) return hipErrorInvalidValue;
   dim3 grid((M + TM - 1) / TM, (N + TN_ - 1) / TN_, fv_tn_xhat_slices(R));
-  hipLaunchKernelGGL(gemm_tn_xhat_kernel, grid, dim3(256), 0, stream,
-                     A, x, mean, rstd, part, db_part, R, M, N);
+#define TN_LAUNCH(D)                                                      \
+  hipLaunchKernelGGL(gemm_tn_xhat_kernel<D>, grid, dim3(256), 0, stream, \
+                     A, x, mean, rstd, part, db_part, R, M, N)
+  if (variant) TN_LAUNCH(TN_DIST);
+  else TN_LAUNCH(0);
+#undef TN_LAUNCH
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// One reduce launch for n <= 4 sliced TN problems that share the slice
+// count z (gemm_tn / gemm_tn_pair calls with reduce = 0 over a common R):
+// out_i(M_i,N_i) (+)= sum_z part_i[z], db_i(M_i) (+)= sum_z db_part_i[z]
+// where db_i is not null. Each element's sum is the one the problem's own
+// reduce launch forms. z <= 1: the GEMMs wrote out/db themselves, nothing
+// is launched.
+hipError_t fv_tn_reduce_list(int n, const float* const* part,
+                             float* const* out, const float* const* db_part,
+                             float* const* db, const int* M, const int* N,
+                             int z, int accumulate, hipStream_t stream) {
+  if (n < 1 || n > TN_LIST_MAX) return hipErrorInvalidValue;
+  if (z <= 1) return hipSuccess;
+  TnReduceList L = {};
+  L.n = n;
+  long blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    L.it[i] = {part[i], out[i], db_part[i], db[i], M[i], N[i]};
+    blocks += tn_reduce_blocks(L.it[i]);
+  }
+  hipLaunchKernelGGL(tn_reduce_list_kernel, dim3((unsigned)blocks), dim3(256),
+                     0, stream, L, z, accumulate);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -17,21 +17,33 @@ hipError_t fv_gemm_nt(const float* A, const float* W, const float* bias,
 hipError_t fv_gemm_nn(const float* A, const float* B, const float* bias,
                       float* out, int R, int Ci, int Co, float alpha,
                       int accumulate, int act_lrelu, const float* lrelu_bwd_of,
-                      hipStream_t stream);
+                      int variant, hipStream_t stream);
+// the dxln GEMM with fv_ln_bwd_params' partials as its only output; *ran = 0
+// (nothing launched) unless fv_ln_bwd_rows(R, C) is 64
+hipError_t fv_gemm_nn_ln(const float* A, const float* B, const float* x,
+                         const float* mean, const float* rstd, float* part,
+                         long R, int Ci, int C, float alpha, int* ran,
+                         hipStream_t stream);
 hipError_t fv_gemm_tn(const float* A, const float* B, float* out, float* part,
                       float* db, float* db_part, int R, int M, int N,
-                      int r_chunks, int accumulate, hipStream_t stream);
+                      int r_chunks, int accumulate, int variant, int reduce,
+                      hipStream_t stream);
 hipError_t fv_gemm_tn_pair(const float* A0, const float* B0, float* out0,
                            float* part0, float* db0, float* db_part0, int N0,
                            const float* A1, const float* B1, float* out1,
                            float* part1, float* db1, float* db_part1, int N1,
                            int R, int M, int r_chunks, int accumulate,
-                           hipStream_t stream);
+                           int variant, int reduce, hipStream_t stream);
+hipError_t fv_tn_reduce_list(int n, const float* const* part,
+                             float* const* out, const float* const* db_part,
+                             float* const* db, const int* M, const int* N,
+                             int z, int accumulate, hipStream_t stream);
 // number of R slices fv_gemm_tn_xhat writes
 int fv_tn_xhat_slices(int R);
 hipError_t fv_gemm_tn_xhat(const float* A, const float* x, const float* mean,
                            const float* rstd, float* part, float* db_part,
-                           int R, int M, int N, hipStream_t stream);
+                           int R, int M, int N, int variant,
+                           hipStream_t stream);
 hipError_t fv_ln_w1x_finish(const float* part, const float* db_part,
                             const float* W1x, const float* gamma,
                             const float* beta, float* gW1x, float* gb1x,
@@ -114,10 +126,16 @@ hipError_t fv_extractor_head_fwd(const float* x, const float* gamma,
                                  hipStream_t stream);
 // row chunks of fv_ln_bwd_params; `part` holds 2C floats for each
 int fv_ln_bwd_yblocks(long R, int C);
+// rows per row chunk of fv_ln_bwd_params
+int fv_ln_bwd_rows(long R, int C);
 hipError_t fv_ln_bwd_params(const float* x, const float* dxln,
                             const float* mean, const float* rstd, float* part,
                             float* dgamma, float* dbeta, long R, int C,
                             int r_chunks, hipStream_t stream);
+// the second kernel of fv_ln_bwd_params alone: dgamma, dbeta from the
+// partials of fv_ln_bwd_yblocks(R, C) row chunks
+hipError_t fv_ln_bwd_reduce(const float* part, float* dgamma, float* dbeta,
+                            long R, int C, hipStream_t stream);
 
 // ---- gru.hip ----------------------------------------------------------
 hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,

@@ -1582,10 +1582,12 @@ class FusedTrainer:
         return iw
 
     def _launch_predict_many(self, iw, R: int, Nn: int, D: int, T: int,
-                             max_n: int, with_beta: bool):
+                             max_n: int, with_beta: bool,
+                             prior_dec: bool = True):
         """Kernel sequence of one packed chunk: extractor head of the
         engine's dtype over all rows -> GRU without backward state ->
-        segmented prior attention -> segmented decoder."""
+        segmented prior attention -> segmented decoder (prior_dec=False
+        stops behind the attention: loss_many decodes the posterior only)."""
         ext, p = self.ext, self.p
         C, H = self.C, self.H
         x2d = iw["x"][:R]
@@ -1621,12 +1623,121 @@ class FusedTrainer:
                          self.p_bv, p("Wl"), p("bl"), p("wmu_p"), p("bmu_p"),
                          p("wsig_p"), p("bsig_p"), iw["pmu"], iw["psig_c"],
                          iw["guard"], alpha)
+        if not prior_dec:
+            return
         out = iw["out"]
         ext.dec_seg_fwd(h, seg, p("W1d"), p("b1d"), p("wmu_d"), p("bmu_d"),
                         p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"), iw["pmu"],
                         iw["psig_c"], iw["eps"][:Nn], out[1, :Nn],
                         out[2, :Nn], out[0, :Nn],
                         iw["beta"][:Nn] if with_beta else None)
+
+    def _launch_posterior(self, iw, Nn: int, D: int, max_n: int,
+                          with_factors: bool):
+        """Posterior steps of one packed chunk, behind
+        _launch_predict_many's attention: segmented encoder -> posterior
+        heads -> segmented decoder fed the posterior rows and the chunk's
+        eps -> segmented loss. Returns the chunk's result as one flat
+        device vector: loss[D] mse[D] kl[D], and with_factors also
+        post_mu, post_sigma, prior_mu, prior_sigma, D*K each."""
+        ext, p = self.ext, self.p
+        M, K = self.M, self.K
+        f = lambda *shape: torch.empty(*shape, device=self.device,
+                                       dtype=torch.float32)
+        # grow-only, sized with the buffers _alloc_infer_ws keeps
+        if iw.get("post_N", 0) < iw["N"]:
+            iw["post_out"] = f(3, iw["N"])  # rows: recon, mu, sigma
+            iw["post_N"] = iw["N"]
+        if iw.get("post_D", 0) < iw["D"]:
+            iw["yp"] = f(iw["D"], M)
+            iw["post"] = f(iw["D"] * (3 + 4 * K))
+            iw["post_D"] = iw["D"]
+        DK = D * K
+        flat = iw["post"]
+        loss, mse, kl = flat[:D], flat[D:2 * D], flat[2 * D:3 * D]
+        fmu = flat[3 * D:3 * D + DK].view(D, K)
+        fsig_c = flat[3 * D + DK:3 * D + 2 * DK].view(D, K)
+        h, seg = iw["h"][:Nn], iw["seg_off"][:D + 1]
+        y, yp, po = iw["label"][:Nn], iw["yp"][:D], iw["post_out"]
+        pmu, psig_c = iw["pmu"][:D], iw["psig_c"][:D]
+        ext.enc_seg_fwd(h, seg, max_n, p("Wenc"), p("benc"), y, yp)
+        ext.enc_seg_heads(yp, p("Wmu_e"), p("bmu_e"), p("Wsig_e"),
+                          p("bsig_e"), fmu, fsig_c)
+        ext.dec_seg_fwd(h, seg, p("W1d"), p("b1d"), p("wmu_d"), p("bmu_d"),
+                        p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"), fmu,
+                        fsig_c, iw["eps"][:Nn], po[1, :Nn], po[2, :Nn],
+                        po[0, :Nn], None)
+        ext.loss_seg(po[0, :Nn], y, seg, fmu, fsig_c, pmu, psig_c, loss, mse,
+                     kl)
+        if not with_factors:
+            return flat[:3 * D]
+        flat[3 * D + 2 * DK:3 * D + 3 * DK].copy_(pmu.reshape(-1))
+        flat[3 * D + 3 * DK:3 * D + 4 * DK].copy_(psig_c.reshape(-1))
+        return flat[:3 * D + 4 * DK]
+
+    @torch.no_grad()
+    def loss_many(self, days, eps=None, sample: bool = True,
+                  return_factors: bool = False,
+                  max_rows: Optional[int] = None):
+        """Per-day validation loss, and optionally the factors, of many
+        trading days in a few launches: the posterior half of the model
+        (encoder q(z | x, y), decoder driven by the posterior factors,
+        MSE + KL against the prior) over the packing of predict_many.
+
+        days: list of (x_d (N_d, T, C), y_d (N_d, 1) or (N_d,)), host or
+        device. eps: optional list of (N_d,) reparameterisation draws;
+        when None they are drawn per chunk with torch's generator, as
+        predict_many does, unless sample=False, which zero-fills them (the
+        reconstruction is then the posterior mean) and leaves torch's
+        generators alone. A given eps is used whatever `sample` says.
+
+        Returns host tensors in input-day order: {"loss", "mse", "kl":
+        (D,) float32, "n": (D,) int32 rows per day}, and with
+        return_factors also "post_mu", "post_sigma", "prior_mu",
+        "prior_sigma": (D, K) — the sigmas as the KL sees them, after the
+        zero clamp. A day without rows has n = 0 and NaN everywhere else.
+
+        Days are chunked exactly as in predict_many (one kernel sequence
+        and one device-to-host copy per chunk) and a day's result does not
+        depend on what it is batched with. Dropout is off, as in
+        validate_epoch. Like predict_many it touches no training buffer,
+        captured graph or in-graph RNG state."""
+        days = list(days)
+        xs = [x for x, _ in days]
+        ys = [y for _, y in days]
+        if eps is not None:
+            eps = list(eps)
+        D_all, K = len(days), self.K
+        nan = float("nan")
+        res = {k: torch.full((D_all,), nan) for k in ("loss", "mse", "kl")}
+        res["n"] = torch.tensor([int(x.shape[0]) for x in xs],
+                                dtype=torch.int32)
+        names = ("post_mu", "post_sigma", "prior_mu", "prior_sigma")
+        if return_factors:
+            for name in names:
+                res[name] = torch.full((D_all, K), nan)
+        for idxs, lens, offs, iw in self._pm_chunks(
+                "loss_many", xs, eps, max_rows, False, ys=ys,
+                draw_eps=sample, prior_dec=False):
+            if iw is None:
+                continue  # days without rows: n = 0, NaN
+            D = len(idxs)
+            host = self._launch_posterior(iw, offs[-1], D, max(lens),
+                                          return_factors).cpu()
+            ii = torch.tensor(idxs)
+            for j, k in enumerate(("loss", "mse", "kl")):
+                res[k][ii] = host[j * D:(j + 1) * D]
+            if return_factors:
+                for j, name in enumerate(names):
+                    o = 3 * D + j * D * K
+                    res[name][ii] = host[o:o + D * K].view(D, K)
+        if return_factors:
+            # an empty day inside a chunk: its factor rows were never
+            # written on the device
+            empty = res["n"] == 0
+            for name in names:
+                res[name][empty] = nan
+        return res
 
     @torch.no_grad()
     def predict_many(self, xs, eps=None, return_dist: bool = False,
@@ -1676,7 +1787,7 @@ class FusedTrainer:
         return results
 
     def _pm_chunks(self, what: str, xs, eps, max_rows, with_beta: bool,
-                   ys=None, draw_eps: bool = True):
+                   ys=None, draw_eps: bool = True, prior_dec: bool = True):
         """The chunk/pack loop shared by predict_many and evaluate_many:
         checks the days, packs them greedily into chunks within max_rows,
         and for each chunk copies the inputs into the inference workspace,
@@ -1684,7 +1795,8 @@ class FusedTrainer:
         the results still on the device. A chunk without any row yields
         iw = None and launches nothing. ys: optional per-day labels, packed
         into iw["label"]. draw_eps=False zero-fills a missing eps instead
-        of drawing it, leaving torch's generator alone."""
+        of drawing it, leaving torch's generator alone. prior_dec=False
+        leaves out the prior decoder (_launch_predict_many)."""
         if self.fp8:
             raise ValueError(f"{what} supports the fp32 and bf16 "
                              "engines; fp8 scoring is not implemented")
@@ -1768,7 +1880,8 @@ class FusedTrainer:
                     iw["label"] = torch.empty(iw["N"], device=self.device)
                 self._pm_pack_rows(iw["label"], [ys[i] for i in idxs], offs,
                                    lens)
-            self._launch_predict_many(iw, R, Nn, D, T, max(lens), with_beta)
+            self._launch_predict_many(iw, R, Nn, D, T, max(lens), with_beta,
+                                      prior_dec)
             yield idxs, lens, offs, iw
 
     @staticmethod
@@ -1805,7 +1918,8 @@ class FusedTrainer:
 
     @torch.no_grad()
     def evaluate_many(self, days, on=("mu",), topk: int = 0, eps=None,
-                      max_rows: Optional[int] = None):
+                      max_rows: Optional[int] = None,
+                      with_loss: bool = False):
         """Per-day IC, RankIC and top-k long/short returns of many trading
         days, computed on the device from the batched scoring workspace.
 
@@ -1824,7 +1938,14 @@ class FusedTrainer:
         prediction or label is not finite are left out and `count` is the
         number of rows used; a day longer than 8192 stocks is reported as
         count = -1 with NaN values. Like predict_many it touches no
-        training buffer, captured graph or in-graph RNG state."""
+        training buffer, captured graph or in-graph RNG state.
+
+        with_loss=True also runs loss_many's posterior steps on each chunk,
+        behind the prior decoder, so the extractor, the GRU and the prior
+        attention run once for both; the result gains "loss", "mse", "kl":
+        (D,) float32 as loss_many returns them. The posterior
+        reconstruction uses the same per-stock eps as the "score" column;
+        when eps is None it is then drawn even for a mu-only evaluation."""
         from ..metrics import check_columns
 
         on = check_columns(on)
@@ -1845,9 +1966,10 @@ class FusedTrainer:
         r_hi = max(row[c] for c in on) + 1
         col = [row[c] - r_lo for c in on]
         Pk = r_hi - r_lo
+        lmk = torch.full((3, D_all), float("nan")) if with_loss else None
         for idxs, lens, offs, iw in self._pm_chunks(
                 "evaluate_many", xs, eps, max_rows, False, ys=ys,
-                draw_eps="score" in on):
+                draw_eps="score" in on or with_loss):
             if iw is None:
                 continue  # days without rows: count 0, NaN
             D, Nn = len(idxs), offs[-1]
@@ -1862,32 +1984,50 @@ class FusedTrainer:
                                   iw["label"][:Nn], iw["seg_off"][:D + 1],
                                   min(max(lens), self.EVAL_MAX_N), topk, st,
                                   cn)
+            if with_loss:
+                # launched ahead of the copies below, which wait
+                post = self._launch_posterior(iw, Nn, D, max(lens), False)
             st_h = st.cpu().view(D, Pk, 4)[:, col]
             cn_h = cn.cpu().view(D, Pk)[:, col]
             ii = torch.tensor(idxs)
             stats[ii] = st_h
             count[ii] = cn_h
-        return {"columns": on, "ic": stats[:, :, 0].clone(),
-                "rank_ic": stats[:, :, 1].clone(),
-                "long": stats[:, :, 2].clone(),
-                "short": stats[:, :, 3].clone(), "count": count}
+            if with_loss:
+                lmk[:, ii] = post.cpu().view(3, D)
+        res = {"columns": on, "ic": stats[:, :, 0].clone(),
+               "rank_ic": stats[:, :, 1].clone(),
+               "long": stats[:, :, 2].clone(),
+               "short": stats[:, :, 3].clone(), "count": count}
+        if with_loss:
+            res["loss"], res["mse"], res["kl"] = (lmk[0].clone(),
+                                                  lmk[1].clone(),
+                                                  lmk[2].clone())
+        return res
 
     @torch.no_grad()
-    def validate_metrics(self, days, topk: int = 0):
+    def validate_metrics(self, days, topk: int = 0, with_loss: bool = False):
         """Summary of evaluate_many on the predictive mean, dropout off:
         {"IC", "ICIR", "RankIC", "RankIC_IR", "long_short", "n_days"}
         (metrics.summarize_ic: means over the days with a finite value,
-        IR = mean / std with ddof=0)."""
+        IR = mean / std with ddof=0). with_loss=True adds "loss": the
+        float64 mean of the finite per-day validation losses of the same
+        pass (evaluate_many(with_loss=True); 0.0 without any)."""
         from ..metrics import summarize_ic
 
         was = self.training
         self.training = False
         try:
-            per_day = self.evaluate_many(days, on=("mu",), topk=topk)
+            per_day = self.evaluate_many(days, on=("mu",), topk=topk,
+                                         with_loss=with_loss)
         finally:
             self.training = was
-        return summarize_ic({k: per_day[k].numpy()
-                             for k in ("ic", "rank_ic", "long", "short")})
+        out = summarize_ic({k: per_day[k].numpy()
+                            for k in ("ic", "rank_ic", "long", "short")})
+        if with_loss:
+            loss = per_day["loss"].double()
+            loss = loss[torch.isfinite(loss)]
+            out["loss"] = float(loss.mean()) if loss.numel() else 0.0
+        return out
 
     # ------------------------------------------------------------- epochs
     # steps per multi-step training graph (real-epoch batching)
@@ -2007,7 +2147,19 @@ class FusedTrainer:
             self._refresh_bf16_shadows()
 
     @torch.no_grad()
-    def validate_epoch(self, days) -> float:
+    def validate_epoch(self, days, batched: bool = False) -> float:
+        """Mean validation loss over the days, dropout off. The default
+        route replays the training-shaped forward once per day.
+        batched=True goes through loss_many instead and returns the
+        float64 host mean of its per-day losses over the days with rows
+        (the fp8 engine, which loss_many refuses, keeps the per-day loop).
+        The two routes draw their decoder noise from different streams
+        (the per-day workspace's in-graph RNG fill against one normal_()
+        per packed chunk): they agree in distribution, not in value."""
+        if batched and not self.fp8:
+            r = self.loss_many(days)
+            loss = r["loss"][r["n"] > 0].double()
+            return float(loss.mean()) if loss.numel() else 0.0
         was = self.training
         self.training = False
         total = torch.zeros((), device=self.device)

@@ -156,7 +156,12 @@ def train_main(args, data_args, df=None) -> float:
     epoch (on the device with the fused engine, metrics.py's oracle with
     the eager one) and logs it; args.select_by = "rankic" (implies
     val_metrics) keeps the checkpoint of the best validation RankIC
-    instead of the lowest validation loss.
+    instead of the lowest validation loss. args.val_batched (fused engine;
+    the eager one ignores it) takes the validation loss from the batched
+    posterior pass, FusedTrainer.validate_epoch(batched=True); together
+    with val_metrics one validate_metrics(with_loss=True) pass over the
+    validation range yields the loss and the ranking metrics. Logged keys
+    and checkpoint selection are the same either way.
 
     Engines (args.engine, default "auto" = fused on GPU, eager on CPU):
     - "fused": the MI355X production path — device-resident epoch cache
@@ -222,6 +227,7 @@ def train_main(args, data_args, df=None) -> float:
     val_metrics = (bool(getattr(args, "val_metrics", False))
                    or select_by == "rankic")
     val_topk = int(getattr(args, "val_topk", 0) or 0)
+    val_batched = bool(getattr(args, "val_batched", False))
 
     if engine == "fused":
         from ..data.device_cache import DeviceEpochCache
@@ -307,7 +313,16 @@ def train_main(args, data_args, df=None) -> float:
             val_days = list(valid_cache.order(0, shuffle=False, rank=rank,
                                               world_size=world_size))
             rate = timer.rate()
-            val_loss = trainer.validate_epoch(val_days)
+            vm = None
+            if val_batched and val_metrics:
+                # one batched pass over the full validation range gives
+                # the loss and the ranking metrics
+                vm = trainer.validate_metrics(valid_cache.days,
+                                              topk=val_topk, with_loss=True)
+                val_loss = vm["loss"]
+            else:
+                val_loss = trainer.validate_epoch(val_days,
+                                                  batched=val_batched)
         else:
             if hasattr(train_dataloader.batch_sampler, "set_epoch"):
                 train_dataloader.batch_sampler.set_epoch(epoch)
@@ -331,7 +346,9 @@ def train_main(args, data_args, df=None) -> float:
         rankic = float("nan")
         if val_metrics:
             if engine == "fused":
-                vm = trainer.validate_metrics(valid_cache.days, topk=val_topk)
+                if vm is None:
+                    vm = trainer.validate_metrics(valid_cache.days,
+                                                  topk=val_topk)
             else:
                 from ..metrics import evaluate_days_eager, summarize_ic
                 vm = summarize_ic(evaluate_days_eager(

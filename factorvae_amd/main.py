@@ -57,6 +57,12 @@ def build_argparser() -> argparse.ArgumentParser:
     parser.add_argument("--val_topk", type=int, default=0,
                         help="with --val_metrics: k > 0 also logs the mean "
                              "top-k minus bottom-k label spread")
+    parser.add_argument("--val_batched", action="store_true",
+                        help="fused engine: validation loss from the batched "
+                             "multi-day posterior pass instead of one graph "
+                             "replay per day; with --val_metrics one pass "
+                             "gives the loss and the ranking metrics (the "
+                             "eager engine ignores the flag)")
     parser.add_argument("--select_by", type=str, default=None,
                         choices=["loss", "rankic"],
                         help="checkpoint selection: lowest validation loss "

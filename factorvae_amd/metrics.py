@@ -123,6 +123,55 @@ def check_columns(on) -> Tuple[str, ...]:
     return on
 
 
+FACTOR_KEYS = ("post_mu", "post_sigma", "prior_mu", "prior_sigma")
+
+
+def loss_days_eager(model, days, eps=None, sample: bool = True,
+                    return_factors: bool = False) -> Dict:
+    """Per-day validation loss and factors of the eager module, from
+    FactorVAE.loss_terms with dropout off: the dict of host tensors
+    FusedTrainer.loss_many returns ("loss", "mse", "kl": (D,) float32,
+    "n": (D,) int32, with return_factors also the four (D, K) factor
+    arrays), and its oracle. days: (x_d (N_d,T,C), y_d) pairs; eps: optional
+    per-day (N_d,) draws, None draws them with torch's generator unless
+    sample=False, which uses zeros. A day without rows is NaN with n = 0."""
+    import torch
+
+    days = list(days)
+    dev = next(model.parameters()).device
+    K = model.factor_encoder.num_factors
+    D = len(days)
+    res = {k: torch.full((D,), NAN) for k in ("loss", "mse", "kl")}
+    res["n"] = torch.tensor([int(x.shape[0]) for x, _ in days],
+                            dtype=torch.int32)
+    if return_factors:
+        for k in FACTOR_KEYS:
+            res[k] = torch.full((D, K), NAN)
+    was = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for d, (x, y) in enumerate(days):
+                n = int(x.shape[0])
+                if n == 0:
+                    continue
+                if eps is not None:
+                    e = torch.as_tensor(eps[d]).to(dev).float().reshape(n, 1)
+                elif sample:
+                    e = None
+                else:
+                    e = torch.zeros(n, 1, device=dev)
+                t = model.loss_terms(
+                    x.to(dev).float(),
+                    torch.as_tensor(y).to(dev).float().reshape(n, 1), e)
+                for k in res:
+                    if k != "n":
+                        res[k][d] = t[k].float().cpu()
+    finally:
+        model.train(was)
+    return res
+
+
 def evaluate_days_eager(model, days, on=("mu",), topk: int = 0) -> Dict:
     """Per-day metrics of the eager module: model.prediction_dist gives
     (mu, sigma); "score" is the stochastic sample mu + eps * sigma with

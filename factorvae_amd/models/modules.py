@@ -299,6 +299,40 @@ class FactorVAE(nn.Module):
         vae_loss = reconstruction_loss + kl_divergence
         return vae_loss, reconstruction, factor_mu, factor_sigma, pred_mu, pred_sigma
 
+    def loss_terms(self, x: torch.Tensor, returns: torch.Tensor, eps=None):
+        """forward's math with the reparameterisation noise as an argument
+        and every term named: a dict with loss, mse, kl (scalars), recon
+        (N, 1) = mu + eps * sigma, and the factors post_mu, post_sigma,
+        prior_mu, prior_sigma (K,). eps: (N, 1) or (N,) standard-normal
+        draws; None draws them the way forward does. Both sigmas come back
+        after their zero clamp (the posterior's is the decoder's, the
+        prior's is forward's): those are the values the KL term sees here.
+        Beyond the reference, whose forward returns the loss only as a
+        sum."""
+        if returns.dim() == 1:
+            returns = returns.unsqueeze(1)
+        stock_latent = self.feature_extractor(x)
+        factor_mu, factor_sigma = self.factor_encoder(stock_latent, returns)
+        mu, sigma = self.factor_decoder.dist(stock_latent, factor_mu,
+                                             factor_sigma)
+        if eps is None:
+            eps = torch.randn_like(sigma)
+        reconstruction = mu + eps.reshape(sigma.shape).to(sigma.dtype) * sigma
+        pred_mu, pred_sigma = self.factor_predictor(stock_latent)
+
+        mse = F.mse_loss(reconstruction, returns)
+        factor_sigma = torch.where(
+            factor_sigma == 0, torch.full_like(factor_sigma, 1e-6), factor_sigma
+        )
+        pred_sigma = torch.where(
+            pred_sigma == 0, torch.full_like(pred_sigma, 1e-6), pred_sigma
+        )
+        kl = self.KL_Divergence(factor_mu, factor_sigma, pred_mu, pred_sigma)
+        return {"loss": mse + kl, "mse": mse, "kl": kl,
+                "recon": reconstruction, "post_mu": factor_mu,
+                "post_sigma": factor_sigma, "prior_mu": pred_mu,
+                "prior_sigma": pred_sigma}
+
     @torch.no_grad()
     def prediction(self, x: torch.Tensor) -> torch.Tensor:
         stock_latent = self.feature_extractor(x)

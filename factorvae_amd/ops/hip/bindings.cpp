@@ -1120,6 +1120,57 @@ void dec_seg_fwd(Tensor h, Tensor seg_off, Tensor W1, Tensor b1, Tensor wmu,
       N, D, K, H, cur_stream()));
 }
 
+// ---- batched multi-day posterior pass ------------------------------
+// h (total,H) and y (total) packed days, seg_off int32 (D+1), max_n the
+// longest day; yp (D,M) gives D. A refused segment comes back as NaN.
+void enc_seg_fwd(Tensor h, Tensor seg_off, long max_n, Tensor Wenc,
+                 Tensor benc, Tensor y, Tensor yp) {
+  OP("enc_seg_fwd", h);
+  const long total = DIM(h, 0), H = DIM(h, 1);
+  op.require(h.dim() == 2, "h must be (total,H)");
+  op.require(DIM(Wenc, 1) == H && Wenc.dim() == 2, "Wenc must be (M,H)");
+  const long M = DIM(Wenc, 0);
+  op.require(DIM(yp, 1) == M && yp.dim() == 2, "yp must be (D,M)");
+  const long D = DIM(yp, 0);
+  op.require(max_n >= 0 && max_n <= total, "max_n outside the packed rows");
+  RUN(fv_enc_seg_fwd(P_F32(h, total * H), P_I32(seg_off, D + 1),
+                     P_F32_EQ(Wenc, M * H), P_F32_EQ(benc, M),
+                     P_F32(y, total), P_F32(yp, D * M), total, D, max_n, M, H,
+                     cur_stream()));
+}
+
+// yp (D,M) -> fmu, fsig_c (D,K): the posterior heads of every day
+void enc_seg_heads(Tensor yp, Tensor Wmu, Tensor bmu, Tensor Wsig,
+                   Tensor bsig, Tensor fmu, Tensor fsig_c) {
+  OP("enc_seg_heads", yp);
+  const long D = DIM(yp, 0), M = DIM(yp, 1);
+  op.require(yp.dim() == 2, "yp must be (D,M)");
+  op.require(DIM(Wmu, 1) == M && Wmu.dim() == 2, "Wmu must be (K,M)");
+  const long K = DIM(Wmu, 0);
+  RUN(fv_enc_seg_heads(P_F32(yp, D * M), P_F32_EQ(Wmu, K * M),
+                       P_F32_EQ(bmu, K), P_F32_EQ(Wsig, K * M),
+                       P_F32_EQ(bsig, K), P_F32(fmu, D * K),
+                       P_F32(fsig_c, D * K), D, M, K, cur_stream()));
+}
+
+// recon / y (total) packed, seg_off int32 (D+1), the four factor tensors
+// (D,K) — fmu gives D and K; loss, mse, kl (D) fp32, NaN for a day without
+// rows or outside the packed buffer
+void loss_seg(Tensor recon, Tensor y, Tensor seg_off, Tensor fmu,
+              Tensor fsig_c, Tensor pmu, Tensor psig_c, Tensor loss,
+              Tensor mse, Tensor kl) {
+  OP("loss_seg", recon);
+  const long total =
+      op.num(op.same_numel(recon, "recon", y, "y"), "recon");
+  const long D = DIM(fmu, 0), K = DIM(fmu, 1);
+  op.require(fmu.dim() == 2, "fmu must be (D,K)");
+  RUN(fv_loss_seg(P_F32(recon, total), P_F32(y, total),
+                  P_I32(seg_off, D + 1), P_F32(fmu, D * K),
+                  P_F32(fsig_c, D * K), P_F32(pmu, D * K),
+                  P_F32(psig_c, D * K), P_F32(loss, D), P_F32(mse, D),
+                  P_F32(kl, D), total, D, K, cur_stream()));
+}
+
 // pred (P,total) fp32 rows with any row stride (a row slice of the scoring
 // workspace's (3,Nn) output), label (>= total) fp32, seg_off int32 (D+1);
 // max_n the longest day (sizes the launch's LDS, <= 8192). Outputs, fully
@@ -1332,6 +1383,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("Wb"), py::arg("bb"), py::arg("fmu"), py::arg("fsig_c"),
           py::arg("eps"), py::arg("mu"), py::arg("sigma"),
           py::arg("sample") = py::none(), py::arg("beta") = py::none());
+  // batched multi-day posterior pass (inference only)
+  mod.def("enc_seg_fwd", &enc_seg_fwd,
+          py::arg("h"), py::arg("seg_off"), py::arg("max_n"),
+          py::arg("Wenc"), py::arg("benc"), py::arg("y"), py::arg("yp"));
+  mod.def("enc_seg_heads", &enc_seg_heads,
+          py::arg("yp"), py::arg("Wmu"), py::arg("bmu"), py::arg("Wsig"),
+          py::arg("bsig"), py::arg("fmu"), py::arg("fsig_c"));
+  mod.def("loss_seg", &loss_seg,
+          py::arg("recon"), py::arg("y"), py::arg("seg_off"), py::arg("fmu"),
+          py::arg("fsig_c"), py::arg("pmu"), py::arg("psig_c"),
+          py::arg("loss"), py::arg("mse"), py::arg("kl"));
   mod.def("daily_ic_seg", &daily_ic_seg,
           py::arg("pred"), py::arg("label"), py::arg("seg_off"),
           py::arg("max_n"), py::arg("topk"), py::arg("stats"),

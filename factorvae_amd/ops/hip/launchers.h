@@ -339,6 +339,21 @@ hipError_t fv_dec_seg_fwd(const float* h, const int* seg_off, const float* W1,
                           float* sigma, float* sample, float* beta, int N,
                           int D, int K, int H, hipStream_t s);
 
+// ---- posterior.hip ----------------------------------------------------
+hipError_t fv_enc_seg_fwd(const float* h, const int* seg_off,
+                          const float* Wenc, const float* benc,
+                          const float* y, float* yp, int total, int D,
+                          int max_n, int M, int H, hipStream_t s);
+hipError_t fv_enc_seg_heads(const float* yp, const float* Wmu,
+                            const float* bmu, const float* Wsig,
+                            const float* bsig, float* fmu, float* fsig_c,
+                            int D, int M, int K, hipStream_t s);
+hipError_t fv_loss_seg(const float* recon, const float* y, const int* seg_off,
+                       const float* fmu, const float* fsig_c,
+                       const float* pmu, const float* psig_c, float* loss,
+                       float* mse, float* kl, int total, int D, int K,
+                       hipStream_t s);
+
 // ---- metrics.hip ------------------------------------------------------
 hipError_t fv_daily_ic_seg(const float* pred, long ld, const float* label,
                            const int* seg_off, double* stats, int* count,

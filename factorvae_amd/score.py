@@ -68,6 +68,11 @@ def build_argparser() -> argparse.ArgumentParser:
                         "write them as JSON next to the score CSV")
     p.add_argument("--metrics_topk", type=int, default=50,
                    help="k of the --metrics long/short spread")
+    p.add_argument("--factors", action="store_true",
+                   help="also write each day's posterior and prior factors "
+                        "(<stem>_factors.csv) and its validation loss terms "
+                        "(<stem>_daily.csv) next to the score CSV; decoder "
+                        "noise off, so the files are reproducible")
     p.add_argument("--topk", type=int, default=50)
     p.add_argument("--n_drop", type=int, default=10)
     return p
@@ -99,6 +104,53 @@ def range_metrics(model, loader, seq_length: int, engine: str = "auto",
         return trainer.validate_metrics(days, topk=topk)
     return summarize_ic(evaluate_days_eager(model, days, on=("mu",),
                                             topk=topk))
+
+
+def range_factors(model, loader, seq_length: int, engine: str = "auto"):
+    """The factors and the validation loss of every day of the loader, with
+    the decoder noise off (the reconstruction is the posterior mean), so
+    the result is reproducible: (factors, daily) DataFrames —
+      factors: one row per (day, factor): datetime, factor, post_mu,
+               post_sigma, prior_mu, prior_sigma (the posterior is the
+               realised factor return given that day's labels);
+      daily:   one row per day: datetime, n_stocks, loss, mse, kl.
+    The fused engine's loss_many on a GPU (engine "auto"/"fused"),
+    metrics.loss_days_eager on the eager module otherwise. Dates come from
+    the dataset's (datetime, instrument) index, walked in loader order as
+    generate_prediction_scores does."""
+    from .engine.trainer import resolve_engine
+    from .metrics import FACTOR_KEYS, loss_days_eager
+
+    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    model.to(device)
+    index = loader.dataset.get_index()
+    days, dates, row = [], [], 0
+    for char_with_label, _ in loader:
+        n = int(char_with_label.shape[0])
+        if char_with_label.shape[1] == seq_length and n > 0:
+            days.append((char_with_label[:, :, :-1].float(),
+                         char_with_label[:, -1, -1].float()))
+            dates.append(index[row][0])
+        row += n
+    hidden = model.feature_extractor.gru.hidden_size
+    if resolve_engine(engine, hidden, device.type, warn=False) == "fused":
+        from .engine.fused import FusedTrainer
+
+        trainer = FusedTrainer(model, lr=0.0, t_max=1, device=device,
+                               train=False)
+        r = trainer.loss_many(days, sample=False, return_factors=True)
+    else:
+        r = loss_days_eager(model, days, sample=False, return_factors=True)
+    D = len(days)
+    K = r["post_mu"].shape[1] if D else 0
+    factors = pd.DataFrame({
+        "datetime": [d for d in dates for _ in range(K)],
+        "factor": list(range(K)) * D,
+        **{k: r[k].reshape(-1).numpy() for k in FACTOR_KEYS}})
+    daily = pd.DataFrame({
+        "datetime": dates, "n_stocks": r["n"].numpy(),
+        **{k: r[k].numpy() for k in ("loss", "mse", "kl")}})
+    return factors, daily
 
 
 def main(argv=None):
@@ -141,6 +193,15 @@ def main(argv=None):
         with open(out_json, "w") as f:
             json.dump(dict(summary, topk=args.metrics_topk), f, indent=1)
         print(f"wrote {out_json}")
+
+    if args.factors:
+        factors, daily = range_factors(model, loader, args.seq_length,
+                                       engine=args.engine)
+        stem = os.path.splitext(out_csv)[0]
+        factors.to_csv(stem + "_factors.csv", index=False)
+        daily.to_csv(stem + "_daily.csv", index=False)
+        print(f"wrote {stem}_factors.csv ({len(factors)} rows) and "
+              f"{stem}_daily.csv ({len(daily)} days)")
 
     if args.backtest:
         merged = scores.join(df[["LABEL0"]], how="inner")

@@ -145,6 +145,10 @@ class FusedTrainer:
         # enc_fused_fwd kernels (bit-identical); FV_MID=0 restores the
         # original kernels
         self._mid = 0 if os.environ.get("FV_MID", "1") == "0" else 1
+        # fp32, H = 64, N <= ext.gru_wave_max_n(): the GRU recurrence with
+        # one wave per stock (variant=1 of gru_fwd / gru_fwd_infer / gru_bwd,
+        # bit-identical); FV_F32_GRU=0 restores the f32 MFMA kernels
+        self._gru_v = 0 if os.environ.get("FV_F32_GRU", "1") == "0" else 1
         # every dtype, N <= 384: the training step's middle chain
         # (docs/KERNELS.md): dec_fwd_bwd -> enc_bwd_mid on main with the loss
         # gradients formed at their consumers, instead of dec_fwd ->
@@ -602,7 +606,8 @@ class FusedTrainer:
                              None, w["h_prev"], w["gates4"], N, T, H)
         else:
             ext.gru_fwd(w["gi"], p("Whh"), p("bhh"), w["h"], None,
-                        w["h_prev"], w["gates4"], N, T, H)
+                        w["h_prev"], w["gates4"], N, T, H,
+                        variant=self._gru_v)
         if self.bf16 and not self._whh_fused:
             # h_prev bf16 image (Whh TN wgrad operand) on side stream 2
             if self.s_side2 is not None:
@@ -931,7 +936,7 @@ class FusedTrainer:
                         w["dgh_bf"].view(N, T, 3 * H))
         else:
             ext.gru_bwd(w["dh"], w["h_prev"], w["gates4"], p("Whh"),
-                        w["dgi"], w["dgh"], N, T, H)
+                        w["dgi"], w["dgh"], N, T, H, variant=self._gru_v)
         if self.bf16:
             fork(1)
             with _on_side(self, 1):
@@ -1616,7 +1621,8 @@ class FusedTrainer:
         if self.bf16 and H == 64:
             ext.gru_fwd_mfma_infer(gi, self.whh_bf, p("bhh"), h, Nn, T, H)
         else:
-            ext.gru_fwd_infer(gi, p("Whh"), p("bhh"), h, Nn, T, H)
+            ext.gru_fwd_infer(gi, p("Whh"), p("bhh"), h, Nn, T, H,
+                              variant=self._gru_v)
         seg = iw["seg_off"][:D + 1]
         alpha = 1.0 / math.sqrt(float(H) + 1e-6)
         ext.attn_seg_fwd(h, seg, max_n, iw["qk"], iw["cb"], self.p_Wv,

@@ -590,28 +590,35 @@ void cast_f32_fp8_scaled(Tensor src, Tensor dst, OptTensor scale) {
 
 // ----------------------------------------------------------------- GRU
 // gi (N,T,3H); h_final (N,H); h_seq / h_prev (N,T,H); gates4 (N,T,4H)
+// variant: 1 = wave-per-stock kernels where they apply (default), 0 = the
+// kernels from before them (bit-identical)
 void gru_fwd(Tensor gi, Tensor Whh, Tensor bhh, Tensor h_final,
              OptTensor h_seq, Tensor h_prev, Tensor gates4, long N, long T,
-             long H) {
+             long H, long variant = 1) {
   OP("gru_fwd", gi);
   NUM(N); NUM(T); NUM(H);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             ", must be 0 or 1");
   RUN(fv_gru_fwd(P_F32(gi, N * T * 3 * H), P_F32_EQ(Whh, 3 * H * H),
                  P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H),
                  P_F32(h_seq, N * T * H), P_F32(h_prev, N * T * H),
-                 P_F32(gates4, N * T * 4 * H), N, T, H, cur_stream()));
+                 P_F32(gates4, N * T * 4 * H), N, T, H, (int)variant,
+                 cur_stream()));
 }
 
 void gru_bwd(Tensor dh_final, Tensor h_prev, Tensor gates4, Tensor Whh,
              Tensor dgi, Tensor dgh, long N, long T, long H,
              OptTensor dgi_bf = c10::nullopt,
-             OptTensor dgh_bf = c10::nullopt) {
+             OptTensor dgh_bf = c10::nullopt, long variant = 1) {
   OP("gru_bwd", dh_final);
   NUM(N); NUM(T); NUM(H);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             ", must be 0 or 1");
   const long G = N * T * 3 * H;
   RUN(fv_gru_bwd(P_F32(dh_final, N * H), P_F32(h_prev, N * T * H),
                  P_F32(gates4, N * T * 4 * H), P_F32_EQ(Whh, 3 * H * H),
                  P_F32(dgi, G), P_F32(dgh, G), P_BF16(dgi_bf, G),
-                 P_BF16(dgh_bf, G), N, T, H, cur_stream()));
+                 P_BF16(dgh_bf, G), N, T, H, (int)variant, cur_stream()));
 }
 
 void gru_fwd_mfma(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
@@ -663,12 +670,14 @@ void gru_bwd_mfma(Tensor dh_final, Tensor h_prev, Tensor gates4,
 
 // Inference forward: h_final only, no backward state
 void gru_fwd_infer(Tensor gi, Tensor Whh, Tensor bhh, Tensor h_final, long N,
-                   long T, long H) {
+                   long T, long H, long variant = 1) {
   OP("gru_fwd_infer", gi);
   NUM(N); NUM(T); NUM(H);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             ", must be 0 or 1");
   RUN(fv_gru_fwd_infer(P_F32(gi, N * T * 3 * H), P_F32_EQ(Whh, 3 * H * H),
                        P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H), N, T, H,
-                       cur_stream()));
+                       (int)variant, cur_stream()));
 }
 
 void gru_fwd_mfma_infer(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
@@ -961,6 +970,7 @@ int as_int(const char* fn, long v) {
 
 // launch geometry, owned by the .hip files: callers size buffers with these
 long dec_nblk(long N) { return fv_dec_nblk(as_int("dec_nblk", N)); }
+long gru_wave_max_n() { return fv_gru_wave_max_n(); }
 long gru_wgrad_blocks(long N) {
   return fv_gru_wgrad_blocks(as_int("gru_wgrad_blocks", N));
 }
@@ -1275,7 +1285,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("absmax_scale", &absmax_scale);
   mod.def("cast_f32_fp8_scaled", &cast_f32_fp8_scaled);
   mod.def("ln_bwd_params", &ln_bwd_params);
-  mod.def("gru_fwd", &gru_fwd);
+  // variant: 1 = wave-per-stock kernels where they apply (default), 0 =
+  // the kernels from before them
+  mod.def("gru_fwd", &gru_fwd, py::arg("gi"), py::arg("Whh"), py::arg("bhh"),
+          py::arg("h_final"), py::arg("h_seq"), py::arg("h_prev"),
+          py::arg("gates4"), py::arg("N"), py::arg("T"), py::arg("H"),
+          py::arg("variant") = 1);
   mod.def("gru_fwd_mfma", &gru_fwd_mfma);
   // variant: 1 = latency-oriented kernel (default), 0 = original kernel
   mod.def("attn_fused_fwd", &attn_fused_fwd,
@@ -1315,6 +1330,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   // launch geometry the .hip files own: block counts that size buffers
   mod.def("dec_nblk", &dec_nblk);
   mod.def("gru_wgrad_blocks", &gru_wgrad_blocks);
+  mod.def("gru_wave_max_n", &gru_wave_max_n);
   mod.def("ln_bwd_yblocks", &ln_bwd_yblocks);
   mod.def("dec_fwd_bwd", &dec_fwd_bwd);
   mod.def("dec_bwd_reduce_heads", &dec_bwd_reduce_heads);
@@ -1334,7 +1350,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gru_bwd", &gru_bwd, py::arg("dh_final"), py::arg("h_prev"),
           py::arg("gates4"), py::arg("Whh"), py::arg("dgi"), py::arg("dgh"),
           py::arg("N"), py::arg("T"), py::arg("H"),
-          py::arg("dgi_bf") = py::none(), py::arg("dgh_bf") = py::none());
+          py::arg("dgi_bf") = py::none(), py::arg("dgh_bf") = py::none(),
+          py::arg("variant") = 1);
   mod.def("enc_softmax_fwd", &enc_softmax_fwd);
   mod.def("enc_softmax_bwd", &enc_softmax_bwd);
   mod.def("enc_heads_fwd", &enc_heads_fwd);
@@ -1369,7 +1386,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("dec_fwd", &dec_fwd);
   mod.def("dec_bwd", &dec_bwd);
   // batched multi-day scoring (inference only)
-  mod.def("gru_fwd_infer", &gru_fwd_infer);
+  mod.def("gru_fwd_infer", &gru_fwd_infer, py::arg("gi"), py::arg("Whh"),
+          py::arg("bhh"), py::arg("h_final"), py::arg("N"), py::arg("T"),
+          py::arg("H"), py::arg("variant") = 1);
   mod.def("gru_fwd_mfma_infer", &gru_fwd_mfma_infer);
   mod.def("attn_seg_fwd", &attn_seg_fwd,
           py::arg("h"), py::arg("seg_off"), py::arg("max_n"), py::arg("qk"),

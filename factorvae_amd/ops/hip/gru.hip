@@ -383,11 +383,22 @@ __global__ __launch_bounds__(512) void gru_bwd_fast_kernel(
 
 extern "C" {
 
-// H == 64 goes to the f32 MFMA recurrence in gru_mfma.hip (exact f32)
+// The wave-per-stock kernels of gru_wave.hip apply at H == 64 up to
+// fv_gru_wave_max_n() stocks (bit-identical to the MFMA kernels).
+static bool use_wave_(int variant, int N, int H) {
+  return variant == 1 && H == 64 && N >= 1 && N <= fv_gru_wave_max_n();
+}
+
+// H == 64 goes to the f32 recurrences in gru_wave.hip (variant 1, small N)
+// or gru_mfma.hip (exact f32, the same bits); variant 0: always gru_mfma.hip
 hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
                       float* h_final, float* h_seq, float* h_prev,
-                      float* gates4, int N, int T, int H, hipStream_t stream) {
+                      float* gates4, int N, int T, int H, int variant,
+                      hipStream_t stream) {
   if (H > 64) return hipErrorInvalidValue;
+  if (use_wave_(variant, N, H))
+    return fv_gru_fwd_wave_f32(gi, Whh, bhh, h_final, h_seq, h_prev, gates4,
+                               N, T, H, stream);
   if (H == 64)
     return fv_gru_fwd_mfma_f32(gi, Whh, bhh, h_final, h_seq, h_prev, gates4,
                                N, T, H, stream);
@@ -410,9 +421,11 @@ hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
 // state written (the SAVE=false instantiations).
 hipError_t fv_gru_fwd_infer(const float* gi, const float* Whh,
                             const float* bhh, float* h_final, int N, int T,
-                            int H, hipStream_t stream) {
+                            int H, int variant, hipStream_t stream) {
   if (H > 64) return hipErrorInvalidValue;
   if (N <= 0) return hipSuccess;
+  if (use_wave_(variant, N, H))
+    return fv_gru_fwd_wave_f32_infer(gi, Whh, bhh, h_final, N, T, H, stream);
   if (H == 64)
     return fv_gru_fwd_mfma_f32_infer(gi, Whh, bhh, h_final, N, T, H, stream);
   if ((H & 3) == 0) {
@@ -435,8 +448,11 @@ hipError_t fv_gru_fwd_infer(const float* gi, const float* Whh,
 hipError_t fv_gru_bwd(const float* dh_final, const float* h_prev,
                       const float* gates4, const float* Whh,
                       float* dgi, float* dgh, void* dgi_bf, void* dgh_bf,
-                      int N, int T, int H, hipStream_t stream) {
+                      int N, int T, int H, int variant, hipStream_t stream) {
   if (H > 64) return hipErrorInvalidValue;
+  if (use_wave_(variant, N, H) && !dgi_bf && !dgh_bf)
+    return fv_gru_bwd_wave_f32(dh_final, h_prev, gates4, Whh, dgi, dgh,
+                               N, T, H, stream);
   if (H == 64 && !dgi_bf && !dgh_bf)
     return fv_gru_bwd_mfma_f32(dh_final, h_prev, gates4, Whh, dgi, dgh,
                                N, T, H, stream);

@@ -138,16 +138,35 @@ hipError_t fv_ln_bwd_reduce(const float* part, float* dgamma, float* dbeta,
                             long R, int C, hipStream_t stream);
 
 // ---- gru.hip ----------------------------------------------------------
+// variant 1: at H == 64, fp32 outputs only and N <= fv_gru_wave_max_n() the
+// wave-per-stock kernels of gru_wave.hip; 0: the kernels from before them.
+// Both give the same bits.
 hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
                       float* h_final, float* h_seq, float* h_prev,
-                      float* gates4, int N, int T, int H, hipStream_t stream);
+                      float* gates4, int N, int T, int H, int variant,
+                      hipStream_t stream);
 hipError_t fv_gru_fwd_infer(const float* gi, const float* Whh,
                             const float* bhh, float* h_final, int N, int T,
-                            int H, hipStream_t stream);
+                            int H, int variant, hipStream_t stream);
 hipError_t fv_gru_bwd(const float* dh_final, const float* h_prev,
                       const float* gates4, const float* Whh, float* dgi,
                       float* dgh, void* dgi_bf, void* dgh_bf, int N, int T,
-                      int H, hipStream_t stream);
+                      int H, int variant, hipStream_t stream);
+
+// ---- gru_wave.hip -----------------------------------------------------
+// largest N at which fv_gru_fwd / _infer / _bwd take the wave kernels
+int fv_gru_wave_max_n(void);
+hipError_t fv_gru_fwd_wave_f32(const float* gi, const float* Whh,
+                               const float* bhh, float* h_final, float* h_seq,
+                               float* h_prev, float* gates4, int N, int T,
+                               int H, hipStream_t stream);
+hipError_t fv_gru_fwd_wave_f32_infer(const float* gi, const float* Whh,
+                                     const float* bhh, float* h_final, int N,
+                                     int T, int H, hipStream_t stream);
+hipError_t fv_gru_bwd_wave_f32(const float* dh_final, const float* h_prev,
+                               const float* gates4, const float* Whh,
+                               float* dgi, float* dgh, int N, int T, int H,
+                               hipStream_t stream);
 
 // ---- gru_mfma.hip -----------------------------------------------------
 // number of workgroups fv_gru_bwd_mfma launches, one wgrad partial each

@@ -8,6 +8,7 @@ from .sampler import (
 )
 from .synthetic import make_synthetic_frame, N_ALPHA_FEATURES
 from .device_cache import DeviceEpochCache
+from .panel import PanelDays
 
 __all__ = [
     "np_ffill",
@@ -19,4 +20,5 @@ __all__ = [
     "make_synthetic_frame",
     "N_ALPHA_FEATURES",
     "DeviceEpochCache",
+    "PanelDays",
 ]

@@ -137,16 +137,24 @@ class TSDataSampler:
                 ids[:, t] = np.where(ids[:, t] < 0, ids[:, t + 1], ids[:, t])
         return ids
 
+    def _rows(self, idx) -> np.ndarray:
+        """Positional indices within [0, len) -> (B,) full-frame rows."""
+        pos = np.asarray(idx, dtype=np.int64) + self.start_idx
+        if len(pos) and (pos.min() < self.start_idx or
+                         pos.max() >= self.end_idx):
+            raise KeyError("index out of bounds")
+        return self.flt_rows[pos] if self.flt_rows is not None else pos
+
+    def window_ids(self, idx) -> np.ndarray:
+        """The (B, T) int64 row numbers into `data_arr` that `self[idx]`
+        gathers for a list or array of positional indices; -1 is the NaN
+        sentinel row. `data_arr[window_ids(idx)]` is `self[idx][0]`."""
+        return self._window_ids(self._rows(idx))
+
     def __getitem__(self, idx):
         if isinstance(idx, (list, np.ndarray)):
-            pos = np.asarray(idx, dtype=np.int64) + self.start_idx
-            if len(pos) and (pos.min() < self.start_idx or
-                             pos.max() >= self.end_idx):
-                raise KeyError("index out of bounds")
-            rows = (self.flt_rows[pos] if self.flt_rows is not None
-                    else pos)
-            ids = self._window_ids(rows)
-            data = self.data_arr[ids]                      # (B, T, C+1)
+            rows = self._rows(idx)
+            data = self.data_arr[self._window_ids(rows)]   # (B, T, C+1)
             actual = self.data.index[rows]
             return data, actual
         rows = np.asarray([self._resolve_pos(idx)], dtype=np.int64)

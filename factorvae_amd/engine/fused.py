@@ -34,6 +34,7 @@ from typing import Dict, Optional
 
 import torch
 
+from ..data.panel import PanelDays
 from ..models.modules import FactorVAE
 from ..ops import get_extension
 from ..parallel.ddp import get_world_size, is_distributed
@@ -1559,11 +1560,16 @@ class FusedTrainer:
             iw["gi"] = f(R, 3 * H)
             iw.pop("xln", None)
             if self.bf16:
-                # same 8-element tail slack as _alloc_ws: the
-                # register-stationary NT kernel's k-tail fragment may read
-                # a few bytes past the last row
+                # zeroed tail slack: the register-stationary NT kernel
+                # reads every row as KP = ceil32(C) elements against
+                # zero-padded weights, so the last row's k-tail fragment
+                # reads KP - C elements past it (2 at C = 158, where
+                # _alloc_ws's 8 suffice; 22 at C = 10), and 0 * garbage
+                # is only 0 for finite garbage
+                slack = self.w1x_p.shape[1] - C + 8
                 fbs = lambda r, c: torch.zeros(
-                    r * c + 8, device=d, dtype=torch.bfloat16)[:r * c].view(r, c)
+                    r * c + slack, device=d,
+                    dtype=torch.bfloat16)[:r * c].view(r, c)
                 iw["xln_bf"] = fbs(R, C)
                 iw["xp_bf"] = fbs(R, C)
             else:
@@ -1586,18 +1592,13 @@ class FusedTrainer:
             iw["D"] = D
         return iw
 
-    def _launch_predict_many(self, iw, R: int, Nn: int, D: int, T: int,
-                             max_n: int, with_beta: bool,
-                             prior_dec: bool = True):
-        """Kernel sequence of one packed chunk: extractor head of the
-        engine's dtype over all rows -> GRU without backward state ->
-        segmented prior attention -> segmented decoder (prior_dec=False
-        stops behind the attention: loss_many decodes the posterior only)."""
+    def _launch_infer_head(self, iw, x2d, gi):
+        """Extractor head of the engine's dtype over the rows of x2d
+        (R, C) into gi (R, 3H), through the inference workspace. Row-local:
+        a row's gi does not depend on where in x2d it stands."""
         ext, p = self.ext, self.p
-        C, H = self.C, self.H
-        x2d = iw["x"][:R]
-        mean, rstd, gi = iw["mean"][:R], iw["rstd"][:R], iw["gi"][:R]
-        h = iw["h"][:Nn]
+        R = x2d.shape[0]
+        mean, rstd = iw["mean"][:R], iw["rstd"][:R]
         if self.bf16:
             xln_bf = iw["xln_bf"][:R]
             xp_bf = iw["xp_bf"][:R]
@@ -1613,16 +1614,37 @@ class FusedTrainer:
                     x2d, p("ln_g"), p("ln_b"), p("W1x"), p("b1x"), p("Wih"),
                     p("bih"), None, mean, rstd, xp, gi, 1e-5)):
                 if "xln" not in iw:
-                    iw["xln"] = torch.empty(iw["R"], C, device=self.device)
+                    iw["xln"] = torch.empty(iw["R"], self.C,
+                                            device=self.device)
                 xln = iw["xln"][:R]
                 ext.ln_fwd(x2d, p("ln_g"), p("ln_b"), xln, mean, rstd, 1e-5)
                 ext.gemm_nt(xln, p("W1x"), p("b1x"), xp, 1.0, False, True)
                 ext.gemm_nt(xp, p("Wih"), p("bih"), gi, 1.0, False, False)
+
+    def _launch_predict_many(self, iw, R: int, Nn: int, D: int, T: int,
+                             max_n: int, with_beta: bool,
+                             prior_dec: bool = True):
+        """Kernel sequence of one packed chunk: extractor head of the
+        engine's dtype over all rows -> GRU without backward state ->
+        _launch_pm_tail."""
+        ext, p, H = self.ext, self.p, self.H
+        gi = iw["gi"][:R]
+        h = iw["h"][:Nn]
+        self._launch_infer_head(iw, iw["x"][:R], gi)
         if self.bf16 and H == 64:
             ext.gru_fwd_mfma_infer(gi, self.whh_bf, p("bhh"), h, Nn, T, H)
         else:
             ext.gru_fwd_infer(gi, p("Whh"), p("bhh"), h, Nn, T, H,
                               variant=self._gru_v)
+        self._launch_pm_tail(iw, Nn, D, max_n, with_beta, prior_dec)
+
+    def _launch_pm_tail(self, iw, Nn: int, D: int, max_n: int,
+                        with_beta: bool, prior_dec: bool = True):
+        """Behind the GRU of one packed chunk: segmented prior attention ->
+        segmented decoder (prior_dec=False stops behind the attention:
+        loss_many decodes the posterior only)."""
+        ext, p, H = self.ext, self.p, self.H
+        h = iw["h"][:Nn]
         seg = iw["seg_off"][:D + 1]
         alpha = 1.0 / math.sqrt(float(H) + 1e-6)
         ext.attn_seg_fwd(h, seg, max_n, iw["qk"], iw["cb"], self.p_Wv,
@@ -1691,7 +1713,9 @@ class FusedTrainer:
         MSE + KL against the prior) over the packing of predict_many.
 
         days: list of (x_d (N_d, T, C), y_d (N_d, 1) or (N_d,)), host or
-        device. eps: optional list of (N_d,) reparameterisation draws;
+        device, or a PanelDays with labels (the same bits as the list of
+        its windows()). eps: optional list of (N_d,) reparameterisation
+        draws;
         when None they are drawn per chunk with torch's generator, as
         predict_many does, unless sample=False, which zero-fills them (the
         reconstruction is then the posterior mean) and leaves torch's
@@ -1708,16 +1732,13 @@ class FusedTrainer:
         depend on what it is batched with. Dropout is off, as in
         validate_epoch. Like predict_many it touches no training buffer,
         captured graph or in-graph RNG state."""
-        days = list(days)
-        xs = [x for x, _ in days]
-        ys = [y for _, y in days]
+        xs, ys, lens_all = self._pm_split_days("loss_many", days)
         if eps is not None:
             eps = list(eps)
-        D_all, K = len(days), self.K
+        D_all, K = len(lens_all), self.K
         nan = float("nan")
         res = {k: torch.full((D_all,), nan) for k in ("loss", "mse", "kl")}
-        res["n"] = torch.tensor([int(x.shape[0]) for x in xs],
-                                dtype=torch.int32)
+        res["n"] = torch.tensor(lens_all, dtype=torch.int32)
         names = ("post_mu", "post_sigma", "prior_mu", "prior_sigma")
         if return_factors:
             for name in names:
@@ -1752,7 +1773,9 @@ class FusedTrainer:
         """Score many trading days in a few launches.
 
         xs: list of (N_d, T, C) tensors (N_d may differ; T and C fixed;
-        host or device). eps: optional list of (N_d,) standard-normal
+        host or device), or a PanelDays, which gives the same bits as the
+        list of its windows() (the extractor head then runs once per
+        referenced row, see _pm_chunks_panel). eps: optional list of (N_d,) standard-normal
         draws; when None they are drawn per chunk with torch's generator.
 
         Returns one entry per day, on the host:
@@ -1772,7 +1795,8 @@ class FusedTrainer:
         batched with. Uses a dedicated inference workspace: training
         buffers, the shape/graph cache and the in-graph RNG state are not
         touched (with eps=None the generator advances, as in predict)."""
-        xs = list(xs)
+        if not isinstance(xs, PanelDays):
+            xs = list(xs)
         if eps is not None:
             eps = list(eps)
         results = [None] * len(xs)
@@ -1802,7 +1826,8 @@ class FusedTrainer:
         iw = None and launches nothing. ys: optional per-day labels, packed
         into iw["label"]. draw_eps=False zero-fills a missing eps instead
         of drawing it, leaving torch's generator alone. prior_dec=False
-        leaves out the prior decoder (_launch_predict_many)."""
+        leaves out the prior decoder (_launch_predict_many). xs may be a
+        PanelDays (_pm_chunks_panel): the same chunks, the same yields."""
         if self.fp8:
             raise ValueError(f"{what} supports the fp32 and bf16 "
                              "engines; fp8 scoring is not implemented")
@@ -1812,7 +1837,12 @@ class FusedTrainer:
         if eps is not None:
             if len(eps) != len(xs):
                 raise ValueError("eps must hold one (N_d,) tensor per day")
-        if not xs:
+        if not len(xs):
+            return
+        if isinstance(xs, PanelDays):
+            yield from self._pm_chunks_panel(what, xs, eps, max_rows,
+                                             with_beta, ys, draw_eps,
+                                             prior_dec)
             return
         T = xs[0].shape[1]
         for i, x in enumerate(xs):
@@ -1829,16 +1859,7 @@ class FusedTrainer:
         if max_rows is None:
             max_rows = (int(os.environ.get("FV_PREDICT_ROWS", "0"))
                         or self.PREDICT_ROWS)
-        # greedy chunking
-        chunks, cur, rows = [], [], 0
-        for i, x in enumerate(xs):
-            r = x.shape[0] * T
-            if cur and rows + r > max_rows:
-                chunks.append(cur)
-                cur, rows = [], 0
-            cur.append(i)
-            rows += r
-        chunks.append(cur)
+        chunks = self._pm_greedy([x.shape[0] for x in xs], T, max_rows)
 
         ext, C = self.ext, self.C
         # everything below runs on the caller's stream: order it after any
@@ -1873,22 +1894,171 @@ class FusedTrainer:
             else:
                 for t, o, n in zip(flat, offs, lens):
                     xd[o * T:(o + n) * T].copy_(t)
-            if eps is None:
-                if draw_eps:
-                    iw["eps"][:Nn].normal_()
-                else:
-                    iw["eps"][:Nn].zero_()
-            else:
-                self._pm_pack_rows(iw["eps"], [eps[i] for i in idxs], offs,
-                                   lens)
-            if ys is not None:
-                if "label" not in iw:
-                    iw["label"] = torch.empty(iw["N"], device=self.device)
-                self._pm_pack_rows(iw["label"], [ys[i] for i in idxs], offs,
-                                   lens)
+            self._pm_pack_eps_labels(iw, idxs, lens, offs, eps, ys, draw_eps)
             self._launch_predict_many(iw, R, Nn, D, T, max(lens), with_beta,
                                       prior_dec)
             yield idxs, lens, offs, iw
+
+    @staticmethod
+    def _pm_split_days(what: str, days):
+        """(xs, ys, rows per day) of a list of (x_d, y_d) or a PanelDays."""
+        if isinstance(days, PanelDays):
+            if days.labels is None:
+                raise ValueError(f"{what} needs a panel with labels")
+            return days, days.labels, days.lens()
+        days = list(days)
+        return ([x for x, _ in days], [y for _, y in days],
+                [int(x.shape[0]) for x, _ in days])
+
+    @staticmethod
+    def _pm_greedy(lens, T: int, max_rows: int):
+        """Day numbers packed greedily into chunks whose sum of N_d * T
+        stays within max_rows; a larger day is its own chunk."""
+        chunks, cur, rows = [], [], 0
+        for i, n in enumerate(lens):
+            r = n * T
+            if cur and rows + r > max_rows:
+                chunks.append(cur)
+                cur, rows = [], 0
+            cur.append(i)
+            rows += r
+        chunks.append(cur)
+        return chunks
+
+    def _pm_pack_eps_labels(self, iw, idxs, lens, offs, eps, ys,
+                            draw_eps: bool):
+        """A chunk's eps (given, drawn over its Nn rows at once, or zero)
+        and labels into the inference workspace."""
+        Nn = offs[-1]
+        if eps is None:
+            if draw_eps:
+                iw["eps"][:Nn].normal_()
+            else:
+                iw["eps"][:Nn].zero_()
+        else:
+            self._pm_pack_rows(iw["eps"], [eps[i] for i in idxs], offs, lens)
+        if ys is not None:
+            if "label" not in iw:
+                iw["label"] = torch.empty(iw["N"], device=self.device)
+            self._pm_pack_rows(iw["label"], [ys[i] for i in idxs], offs,
+                               lens)
+
+    # default row budget of one day block of the panel route: gi_rows is
+    # 768 B per row at H = 64, i.e. 1.5 GiB
+    PANEL_ROWS = 1 << 21
+
+    def _pm_chunks_panel(self, what: str, panel, eps, max_rows,
+                         with_beta: bool, ys, draw_eps: bool,
+                         prior_dec: bool):
+        """_pm_chunks for a PanelDays: the same greedy day chunks (so a
+        seed draws the same eps) and the same yields, but the extractor
+        head runs once per referenced row and the GRU gathers.
+
+        Consecutive chunks form a day block while the row range
+        [lo, hi] they reference holds at most FV_PANEL_ROWS rows. Per
+        block the head runs over rows[lo:hi+1] in slices of at most
+        max_rows rows into the grow-only gi_rows buffer; per chunk the
+        ids, rebased by -lo with negative entries kept, go to the
+        workspace and the gather GRU and _launch_pm_tail run."""
+        T, C, H = panel.T, self.C, self.H
+        lens = panel.lens()
+        if panel.C != C:
+            raise ValueError(f"{what}: the panel's rows have {panel.C} "
+                             f"features, the model {C}")
+        for i, n in enumerate(lens):
+            if eps is not None and eps[i].numel() != n:
+                raise ValueError(f"day {i}: eps must have {n} entries, got "
+                                 f"{eps[i].numel()}")
+        if max_rows is None:
+            max_rows = (int(os.environ.get("FV_PREDICT_ROWS", "0"))
+                        or self.PREDICT_ROWS)
+        budget = (int(os.environ.get("FV_PANEL_ROWS", "0"))
+                  or self.PANEL_ROWS)
+        # day blocks of whole chunks: [lo, hi, chunks]; lo None = no row
+        blocks = []
+        for idxs in self._pm_greedy(lens, T, max_rows):
+            spans = [panel.span[i] for i in idxs if panel.span[i]]
+            lo = min((s[0] for s in spans), default=None)
+            hi = max((s[1] for s in spans), default=None)
+            if spans and hi - lo + 1 > budget:
+                raise ValueError(
+                    f"{what}: days {idxs[0]}..{idxs[-1]} reference a range "
+                    f"of {hi - lo + 1} rows, more than FV_PANEL_ROWS = "
+                    f"{budget}; lower max_rows or raise FV_PANEL_ROWS")
+            b = blocks[-1] if blocks else None
+            if b and not spans:
+                b[2].append(idxs)
+            elif b and b[0] is None:
+                b[0], b[1] = lo, hi
+                b[2].append(idxs)
+            elif b and max(hi, b[1]) - min(lo, b[0]) + 1 <= budget:
+                b[0], b[1] = min(lo, b[0]), max(hi, b[1])
+                b[2].append(idxs)
+            else:
+                blocks.append([lo, hi, [idxs]])
+
+        ext, p, dev = self.ext, self.p, self.device
+        self._main_exit()
+        step = max(int(max_rows), 1)
+        qk_done = False
+        for lo, hi, chunks in blocks:
+            U = 0 if lo is None else hi - lo + 1
+            lo = lo or 0
+            Nn_max = max(sum(lens[i] for i in idxs) for idxs in chunks)
+            if Nn_max == 0:
+                for idxs in chunks:
+                    yield idxs, [0] * len(idxs), [0] * (len(idxs) + 1), None
+                continue
+            iw = self._alloc_infer_ws(min(step, max(U, 1)), Nn_max,
+                                      max(len(idxs) for idxs in chunks),
+                                      with_beta)
+            if iw.get("gi_rows_cap", 0) < max(U, 1):
+                iw["gi_rows"] = torch.empty(max(U, 1), 3 * H, device=dev)
+                iw["gi_rows_cap"] = max(U, 1)
+            if iw.get("pidx_cap", 0) < Nn_max * T:
+                iw["pidx"] = torch.empty(Nn_max * T, device=dev,
+                                         dtype=torch.int32)
+                iw["pidx_cap"] = Nn_max * T
+            gi_rows = iw["gi_rows"]
+            for o in range(0, U, step):
+                r = min(step, U - o)
+                src = panel.rows[lo + o:lo + o + r]
+                if src.device != gi_rows.device:   # host rows: slice by slice
+                    iw["x"][:r].copy_(src)
+                    src = iw["x"][:r]
+                self._launch_infer_head(iw, src, gi_rows[o:o + r])
+            if not qk_done:
+                ext.attn_qk_fwd(self.p_q, self.p_Wk, self.p_bk, iw["qk"],
+                                iw["cb"])
+                qk_done = True
+            for idxs in chunks:
+                cl = [lens[i] for i in idxs]
+                Nn, D = sum(cl), len(idxs)
+                offs = [0]
+                for n in cl:
+                    offs.append(offs[-1] + n)
+                if Nn == 0:
+                    yield idxs, cl, offs, None
+                    continue
+                iw["seg_off"][:D + 1].copy_(
+                    torch.tensor(offs, dtype=torch.int32), non_blocking=False)
+                ids = torch.cat([panel.ids[i] for i in idxs], dim=0)
+                pidx = iw["pidx"][:Nn * T].view(Nn, T)
+                pidx.copy_(torch.where(ids >= 0, ids - lo, ids))
+                self._pm_pack_eps_labels(iw, idxs, cl, offs, eps, ys,
+                                         draw_eps)
+                h = iw["h"][:Nn]
+                if self.bf16 and H == 64:
+                    ext.gru_fwd_mfma_infer_gather(gi_rows, U, pidx,
+                                                  self.whh_bf, p("bhh"), h,
+                                                  Nn, T, H)
+                else:
+                    ext.gru_fwd_infer_gather(gi_rows, U, pidx, p("Whh"),
+                                             p("bhh"), h, Nn, T, H,
+                                             variant=self._gru_v)
+                self._launch_pm_tail(iw, Nn, D, max(cl), with_beta,
+                                     prior_dec)
+                yield idxs, cl, offs, iw
 
     @staticmethod
     def _pm_pack_rows(dst, vals, offs, lens):
@@ -1930,7 +2100,8 @@ class FusedTrainer:
         days, computed on the device from the batched scoring workspace.
 
         days: list of (x_d (N_d, T, C), y_d (N_d, 1) or (N_d,)), host or
-        device. on: the prediction columns to rank on, a subset of
+        device, or a PanelDays with labels (the same bits as the list of
+        its windows()). on: the prediction columns to rank on, a subset of
         ("score", "mu") — the stochastic sample and the predictive mean.
         eps as in predict_many; when None, "score" draws it and a
         mu-only evaluation leaves torch's generator alone.
@@ -1958,12 +2129,10 @@ class FusedTrainer:
         topk = int(topk)
         if topk < 0:
             raise ValueError(f"topk must be >= 0, got {topk}")
-        days = list(days)
-        xs = [x for x, _ in days]
-        ys = [y for _, y in days]
+        xs, ys, lens_all = self._pm_split_days("evaluate_many", days)
         if eps is not None:
             eps = list(eps)
-        D_all, P = len(days), len(on)
+        D_all, P = len(lens_all), len(on)
         stats = torch.full((D_all, P, 4), float("nan"), dtype=torch.float64)
         count = torch.zeros(D_all, P, dtype=torch.int32)
         # rows of iw["out"]: sample, mu, sigma

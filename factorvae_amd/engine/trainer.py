@@ -160,8 +160,11 @@ def train_main(args, data_args, df=None) -> float:
     the eager one ignores it) takes the validation loss from the batched
     posterior pass, FusedTrainer.validate_epoch(batched=True); together
     with val_metrics one validate_metrics(with_loss=True) pass over the
-    validation range yields the loss and the ranking metrics. Logged keys
-    and checkpoint selection are the same either way.
+    validation range yields the loss and the ranking metrics.
+    args.val_panel (implies val_batched) holds the validation range as a
+    data.panel.PanelDays, each (stock, date) row once, and sends those
+    passes through the panel route; every rank then validates the whole
+    range. Logged keys and checkpoint selection are the same either way.
 
     Engines (args.engine, default "auto" = fused on GPU, eager on CPU):
     - "fused": the MI355X production path — device-resident epoch cache
@@ -228,9 +231,16 @@ def train_main(args, data_args, df=None) -> float:
                    or select_by == "rankic")
     val_topk = int(getattr(args, "val_topk", 0) or 0)
     val_batched = bool(getattr(args, "val_batched", False))
+    # the validation range as a PanelDays (implies val_batched); the fp8
+    # engine has no batched validation to send it through
+    val_panel = (bool(getattr(args, "val_panel", False))
+                 and engine == "fused"
+                 and getattr(args, "dtype", "fp32") != "fp8")
+    val_batched = val_batched or val_panel
 
     if engine == "fused":
         from ..data.device_cache import DeviceEpochCache
+        from ..data.panel import PanelDays
         from .fused import FusedTrainer
 
         # unsharded loaders -> every rank caches all days once (288 GB
@@ -242,11 +252,18 @@ def train_main(args, data_args, df=None) -> float:
             start=data_args.start_time, end=data_args.fit_end_time,
             select_feature=data_args.select_feature, num_workers=nw),
             device, seed=args.seed)
-        valid_cache = DeviceEpochCache(init_data_loader(
+        valid_loader = init_data_loader(
             df, shuffle=False, step_len=data_args.seq_len,
             start=data_args.val_start_time, end=data_args.val_end_time,
-            select_feature=data_args.select_feature, num_workers=nw),
-            device, seed=args.seed)
+            select_feature=data_args.select_feature, num_workers=nw)
+        if val_panel:
+            # every rank holds the whole range once per (stock, date) row
+            # and validates all of it
+            valid_days = PanelDays.from_loader(valid_loader).to(device)
+        else:
+            valid_cache = DeviceEpochCache(valid_loader, device,
+                                           seed=args.seed)
+            valid_days = valid_cache.days
 
         steps_per_epoch = train_cache.num_batches(rank, world_size)
         trainer = FusedTrainer(factorVAE, lr=args.lr,
@@ -310,17 +327,19 @@ def train_main(args, data_args, df=None) -> float:
                                           world_size=world_size))
             train_loss = trainer.train_epoch(days)
             timer.tick(len(days))
-            val_days = list(valid_cache.order(0, shuffle=False, rank=rank,
-                                              world_size=world_size))
             rate = timer.rate()
             vm = None
             if val_batched and val_metrics:
                 # one batched pass over the full validation range gives
                 # the loss and the ranking metrics
-                vm = trainer.validate_metrics(valid_cache.days,
-                                              topk=val_topk, with_loss=True)
+                vm = trainer.validate_metrics(valid_days, topk=val_topk,
+                                              with_loss=True)
                 val_loss = vm["loss"]
+            elif val_panel:
+                val_loss = trainer.validate_epoch(valid_days, batched=True)
             else:
+                val_days = list(valid_cache.order(0, shuffle=False, rank=rank,
+                                                  world_size=world_size))
                 val_loss = trainer.validate_epoch(val_days,
                                                   batched=val_batched)
         else:
@@ -347,8 +366,7 @@ def train_main(args, data_args, df=None) -> float:
         if val_metrics:
             if engine == "fused":
                 if vm is None:
-                    vm = trainer.validate_metrics(valid_cache.days,
-                                                  topk=val_topk)
+                    vm = trainer.validate_metrics(valid_days, topk=val_topk)
             else:
                 from ..metrics import evaluate_days_eager, summarize_ic
                 vm = summarize_ic(evaluate_days_eager(

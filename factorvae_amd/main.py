@@ -63,6 +63,12 @@ def build_argparser() -> argparse.ArgumentParser:
                              "replay per day; with --val_metrics one pass "
                              "gives the loss and the ranking metrics (the "
                              "eager engine ignores the flag)")
+    parser.add_argument("--val_panel", action="store_true",
+                        help="fused engine: hold the validation range once "
+                             "per (stock, date) row instead of as windows "
+                             "and validate through the panel route (implies "
+                             "--val_batched; the eager engine ignores the "
+                             "flag)")
     parser.add_argument("--select_by", type=str, default=None,
                         choices=["loss", "rankic"],
                         help="checkpoint selection: lowest validation loss "

@@ -690,6 +690,33 @@ void gru_fwd_mfma_infer(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
                             H, cur_stream()));
 }
 
+// The gather forms: gi_rows (U,3H), idx int32 (N,T); step t of stock n reads
+// row idx[n*T + t], an index outside [0,U) is a missing row (NaN h_final)
+void gru_fwd_infer_gather(Tensor gi_rows, long U, Tensor idx, Tensor Whh,
+                          Tensor bhh, Tensor h_final, long N, long T, long H,
+                          long variant = 1) {
+  OP("gru_fwd_infer_gather", gi_rows);
+  NUM(U); NUM(N); NUM(T); NUM(H);
+  op.require(variant == 0 || variant == 1, "variant = ", variant,
+             ", must be 0 or 1");
+  RUN(fv_gru_fwd_infer_gather(P_F32(gi_rows, U * 3 * H), U, P_I32(idx, N * T),
+                              P_F32_EQ(Whh, 3 * H * H), P_F32_EQ(bhh, 3 * H),
+                              P_F32(h_final, N * H), N, T, H, (int)variant,
+                              cur_stream()));
+}
+
+void gru_fwd_mfma_infer_gather(Tensor gi_rows, long U, Tensor idx,
+                               Tensor whh_bf, Tensor bhh, Tensor h_final,
+                               long N, long T, long H) {
+  OP("gru_fwd_mfma_infer_gather", gi_rows);
+  NUM(U); NUM(N); NUM(T); NUM(H);
+  RUN(fv_gru_fwd_mfma_infer_gather(P_F32(gi_rows, U * 3 * H), U,
+                                   P_I32(idx, N * T),
+                                   P_BF16_EQ(whh_bf, 3 * H * H),
+                                   P_F32_EQ(bhh, 3 * H), P_F32(h_final, N * H),
+                                   N, T, H, cur_stream()));
+}
+
 // ------------------------------------------------------------ attention
 // h (N,H); qk (K,H); per-head weights Wv (K,H,H), bv (K,H); the predictor
 // MLP Wl (H,H), bl / wmu / wsig (H), bmu / bsig (1); a / sd / mask (N,K);
@@ -1390,6 +1417,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("bhh"), py::arg("h_final"), py::arg("N"), py::arg("T"),
           py::arg("H"), py::arg("variant") = 1);
   mod.def("gru_fwd_mfma_infer", &gru_fwd_mfma_infer);
+  mod.def("gru_fwd_infer_gather", &gru_fwd_infer_gather, py::arg("gi_rows"),
+          py::arg("U"), py::arg("idx"), py::arg("Whh"), py::arg("bhh"),
+          py::arg("h_final"), py::arg("N"), py::arg("T"), py::arg("H"),
+          py::arg("variant") = 1);
+  mod.def("gru_fwd_mfma_infer_gather", &gru_fwd_mfma_infer_gather);
   mod.def("attn_seg_fwd", &attn_seg_fwd,
           py::arg("h"), py::arg("seg_off"), py::arg("max_n"), py::arg("qk"),
           py::arg("cb"), py::arg("Wv"), py::arg("bv"), py::arg("Wl"),

@@ -18,13 +18,15 @@
 // [r, z, n, q].
 
 #include "common.h"
+#include "gru_gather.h"
 #include "launchers.h"
 
 #define GRU_SPW 4  // stocks per workgroup (= waves)
 
 // SAVE=false (inference): the backward state (h_seq, h_prev, gates4) is
-// neither written nor touched; the pointers may be null.
-template <bool SAVE>
+// neither written nor touched; the pointers may be null. GATHER
+// (gru_gather.h): gi is (U,3H) and step t of stock s reads row idx[s*T + t].
+template <bool SAVE, bool GATHER = false>
 __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
     const float* __restrict__ gi,     // (N,T,3H)
     const float* __restrict__ Whh,    // (3H,H)
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
     float* __restrict__ h_seq,        // (N,T,H)
     float* __restrict__ h_prev_out,   // (N,T,H)
     float* __restrict__ gates4,       // (N,T,4H)
-    int N, int T, int H) {
+    int N, int T, int H, const int* __restrict__ idx, int U) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* WhhT = (float*)smem;                   // [H][3H] transposed
   float* hprev = WhhT + (size_t)H * 3 * H;      // [GRU_SPW][H]
@@ -59,6 +61,8 @@ __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
   for (int t = 0; t < T; ++t) {
     float hn = 0.0f;
     if (live) {
+      // the gather form's row number, loaded ahead of the dot products
+      const int ix = GATHER ? idx[(long)s * T + t] : 0;
       float ghr = br, ghz = bz, q = bn;
       const float* hp = &hprev[w * H];
       for (int i = 0; i < H; ++i) {
@@ -68,10 +72,15 @@ __global__ __launch_bounds__(256) void gru_fwd_generic_kernel(
         ghz = fmaf(hv, wrow[H + lane], ghz);
         q = fmaf(hv, wrow[2 * H + lane], q);
       }
-      const long base = ((long)s * T + t) * 3 * H;
-      const float gir = gi[base + lane];
-      const float giz = gi[base + H + lane];
-      const float gin = gi[base + 2 * H + lane];
+      float gir, giz, gin;
+      if (GATHER) {
+        gather3_(gi, ix, U, H, lane, gir, giz, gin);
+      } else {
+        const long base = ((long)s * T + t) * 3 * H;
+        gir = gi[base + lane];
+        giz = gi[base + H + lane];
+        gin = gi[base + 2 * H + lane];
+      }
       const float r = sigmoidf_(gir + ghr);
       const float z = sigmoidf_(giz + ghz);
       const float n = tanhf_(fmaf(r, q, gin));
@@ -191,12 +200,13 @@ __global__ __launch_bounds__(256) void gru_bwd_generic_kernel(
 //      groups hit disjoint bank quads (bank = j*4 % 64), conflict-free.
 #define GRU_SPW_F 8
 
-template <bool SAVE>
+template <bool SAVE, bool GATHER = false>
 __global__ __launch_bounds__(512) void gru_fwd_fast_kernel(
     const float* __restrict__ gi, const float* __restrict__ Whh,
     const float* __restrict__ bhh, float* __restrict__ h_final,
     float* __restrict__ h_seq, float* __restrict__ h_prev_out,
-    float* __restrict__ gates4, int N, int T, int H) {
+    float* __restrict__ gates4, int N, int T, int H,
+    const int* __restrict__ idx, int U) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* WT4 = (float*)smem;                       // [H/4][3][64][4]
   float* hprev = WT4 + (size_t)3 * 64 * H;         // [GRU_SPW_F][64]
@@ -227,7 +237,12 @@ __global__ __launch_bounds__(512) void gru_fwd_fast_kernel(
 
   // prefetch t=0 gate-input rows so global latency hides under the dot
   float gir = 0.f, giz = 0.f, gin = 0.f;
-  if (live) {
+  WaveIdx wi;   // every lane of the wave takes part in at()
+  if (GATHER) {
+    wi.init(idx + (long)s * T, s < N ? T : 0, lane);
+    const int ix = wi.at(0, lane);
+    if (live) gather3_(gi, ix, U, H, lane, gir, giz, gin);
+  } else if (live) {
     const long b0 = (long)s * T * 3 * H;
     gir = gi[b0 + lane];
     giz = gi[b0 + H + lane];
@@ -236,7 +251,10 @@ __global__ __launch_bounds__(512) void gru_fwd_fast_kernel(
   for (int t = 0; t < T; ++t) {
     float hn = 0.0f;
     float nir = 0.f, niz = 0.f, nin = 0.f;
-    if (live && t + 1 < T) {
+    if (GATHER) {
+      const int ix = t + 1 < T ? wi.at(t + 1, lane) : -1;
+      if (live) gather3_(gi, ix, U, H, lane, nir, niz, nin);
+    } else if (live && t + 1 < T) {
       const long bnx = ((long)s * T + t + 1) * 3 * H;
       nir = gi[bnx + lane];
       niz = gi[bnx + H + lane];
@@ -406,12 +424,14 @@ hipError_t fv_gru_fwd(const float* gi, const float* Whh, const float* bhh,
     const size_t lds = ((size_t)3 * 64 * H + GRU_SPW_F * 64) * sizeof(float);
     dim3 grid((N + GRU_SPW_F - 1) / GRU_SPW_F);
     hipLaunchKernelGGL(gru_fwd_fast_kernel<true>, grid, dim3(512), lds, stream,
-                       gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H);
+                       gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H,
+                       nullptr, 0);
   } else {
     const size_t lds = ((size_t)H * 3 * H + GRU_SPW * H) * sizeof(float);
     dim3 grid((N + GRU_SPW - 1) / GRU_SPW);
     hipLaunchKernelGGL(gru_fwd_generic_kernel<true>, grid, dim3(256), lds, stream,
-                       gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H);
+                       gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T, H,
+                       nullptr, 0);
   }
   HIP_CHECK_LAST();
   return hipSuccess;
@@ -433,13 +453,45 @@ hipError_t fv_gru_fwd_infer(const float* gi, const float* Whh,
     dim3 grid((N + GRU_SPW_F - 1) / GRU_SPW_F);
     hipLaunchKernelGGL(gru_fwd_fast_kernel<false>, grid, dim3(512), lds,
                        stream, gi, Whh, bhh, h_final, nullptr, nullptr,
-                       nullptr, N, T, H);
+                       nullptr, N, T, H, nullptr, 0);
   } else {
     const size_t lds = ((size_t)H * 3 * H + GRU_SPW * H) * sizeof(float);
     dim3 grid((N + GRU_SPW - 1) / GRU_SPW);
     hipLaunchKernelGGL(gru_fwd_generic_kernel<false>, grid, dim3(256), lds,
                        stream, gi, Whh, bhh, h_final, nullptr, nullptr,
-                       nullptr, N, T, H);
+                       nullptr, N, T, H, nullptr, 0);
+  }
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+// fv_gru_fwd_infer with gathered gate inputs (gru_gather.h): the same
+// dispatch, and with equal gate inputs the same h_final bits.
+hipError_t fv_gru_fwd_infer_gather(const float* gi_rows, int U,
+                                   const int* idx, const float* Whh,
+                                   const float* bhh, float* h_final, int N,
+                                   int T, int H, int variant,
+                                   hipStream_t stream) {
+  if (H > 64 || U < 0) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  if (use_wave_(variant, N, H))
+    return fv_gru_fwd_wave_f32_infer_gather(gi_rows, U, idx, Whh, bhh,
+                                            h_final, N, T, H, stream);
+  if (H == 64)
+    return fv_gru_fwd_mfma_f32_infer_gather(gi_rows, U, idx, Whh, bhh,
+                                            h_final, N, T, H, stream);
+  if ((H & 3) == 0) {
+    const size_t lds = ((size_t)3 * 64 * H + GRU_SPW_F * 64) * sizeof(float);
+    dim3 grid((N + GRU_SPW_F - 1) / GRU_SPW_F);
+    hipLaunchKernelGGL((gru_fwd_fast_kernel<false, true>), grid, dim3(512),
+                       lds, stream, gi_rows, Whh, bhh, h_final, nullptr,
+                       nullptr, nullptr, N, T, H, idx, U);
+  } else {
+    const size_t lds = ((size_t)H * 3 * H + GRU_SPW * H) * sizeof(float);
+    dim3 grid((N + GRU_SPW - 1) / GRU_SPW);
+    hipLaunchKernelGGL((gru_fwd_generic_kernel<false, true>), grid,
+                       dim3(256), lds, stream, gi_rows, Whh, bhh, h_final,
+                       nullptr, nullptr, nullptr, N, T, H, idx, U);
   }
   HIP_CHECK_LAST();
   return hipSuccess;

@@ -19,6 +19,7 @@
 // h_prev, gates4=[r,z,n,q] fp32 (+ optional bf16 dgi/dgh copies).
 
 #include "common.h"
+#include "gru_gather.h"
 #include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -30,9 +31,44 @@ typedef __attribute__((address_space(3))) s16x4_g* lds_v4p_g;
 #define GM_HB 72      // bf16 h image row stride (16B-aligned frags)
 #define GM_GB 200     // bf16 dgh image row stride
 
+// Step t's gate inputs of the elementwise phase's thread (stock row erow,
+// units ej..ej+3). GATHER (gru_gather.h): gi is (U,192) and the step reads
+// row idx[erow + t] of it; nix carries that number from the call before,
+// so the index load is never in front of the loads it addresses.
+template <bool GATHER>
+DEVINL void gm_gi_load_(const float* __restrict__ gi,
+                        const int* __restrict__ idx, int U, long erow, int t,
+                        int T, int ej, int& nix, float (&pgr)[4],
+                        float (&pgz)[4], float (&pgn)[4]) {
+  if (GATHER) {
+    const int ix = nix;
+    if (t + 1 < T) nix = idx[erow + t + 1];
+    const bool ok = (unsigned)ix < (unsigned)U;   // else a missing row
+    const float* g = gi + (ok ? (long)ix * 192 : 0L);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      pgr[u] = pgz[u] = pgn[u] = __builtin_nanf("");
+      if (ok) {
+        pgr[u] = g[ej + u];
+        pgz[u] = g[64 + ej + u];
+        pgn[u] = g[128 + ej + u];
+      }
+    }
+  } else {
+    const float* g = gi + (erow + t) * 192;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      pgr[u] = g[ej + u];
+      pgz[u] = g[64 + ej + u];
+      pgn[u] = g[128 + ej + u];
+    }
+  }
+}
+
 // SAVE=false (inference): no h_seq / h_prev / gates4 stores; the pointers
-// may be null.
-template <bool SAVE>
+// may be null. GATHER: see gm_gi_load_; without it idx and U are not looked
+// at.
+template <bool SAVE, bool GATHER = false>
 __global__ __launch_bounds__(256) void gru_fwd_mfma_kernel(
     const float* __restrict__ gi,      // (N,T,192)
     const void* __restrict__ whh_bf_,  // (192,64) bf16
@@ -41,7 +77,7 @@ __global__ __launch_bounds__(256) void gru_fwd_mfma_kernel(
     float* __restrict__ h_seq,         // (N,T,64)
     float* __restrict__ h_prev_out,    // (N,T,64)
     float* __restrict__ gates4,        // (N,T,256)
-    int N, int T) {
+    int N, int T, const int* __restrict__ idx, int U) {
   const __bf16* whh_bf = (const __bf16*)whh_bf_;
   __shared__ __bf16 hB[GM_S][GM_HB];   // bf16 h image (A-frags)
   __shared__ float hS[GM_S][64];       // fp32 h state
@@ -79,16 +115,10 @@ __global__ __launch_bounds__(256) void gru_fwd_mfma_kernel(
 
   // per-thread gi prefetch registers (12 floats: r,z,n x 4 units)
   float pgr[4], pgz[4], pgn[4];
+  int nix = (GATHER && elive && T > 0) ? idx[erow] : -1;
   auto gi_load = [&](int t) {
-    if (elive) {
-      const float* g = gi + (erow + t) * 192;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        pgr[u] = g[ej + u];
-        pgz[u] = g[64 + ej + u];
-        pgn[u] = g[128 + ej + u];
-      }
-    }
+    if (elive)
+      gm_gi_load_<GATHER>(gi, idx, U, erow, t, T, ej, nix, pgr, pgz, pgn);
   };
   gi_load(0);
 
@@ -427,12 +457,13 @@ __global__ __launch_bounds__(256) void gru_bwd_mfma_kernel(
 // registers: 48 floats/lane fwd (3 n-tiles x 16 k-steps), 48 bwd.
 #define GMF_SH 68   // fp32 h image stride (2-way worst-case banks)
 
-template <bool SAVE>
+template <bool SAVE, bool GATHER = false>
 __global__ __launch_bounds__(256) void gru_fwd_mfma_f32_kernel(
     const float* __restrict__ gi, const float* __restrict__ Whh,
     const float* __restrict__ bhh, float* __restrict__ h_final,
     float* __restrict__ h_seq, float* __restrict__ h_prev_out,
-    float* __restrict__ gates4, int N, int T) {
+    float* __restrict__ gates4, int N, int T, const int* __restrict__ idx,
+    int U) {
   __shared__ float hS[GM_S][GMF_SH];
   __shared__ float ghS[GM_S][192];
 
@@ -463,16 +494,10 @@ __global__ __launch_bounds__(256) void gru_fwd_mfma_f32_kernel(
   const long erow = (long)(s0 + es) * T;
 
   float pgr[4], pgz[4], pgn[4];
+  int nix = (GATHER && elive && T > 0) ? idx[erow] : -1;
   auto gi_load = [&](int t) {
-    if (elive) {
-      const float* g = gi + (erow + t) * 192;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        pgr[u] = g[ej + u];
-        pgz[u] = g[64 + ej + u];
-        pgn[u] = g[128 + ej + u];
-      }
-    }
+    if (elive)
+      gm_gi_load_<GATHER>(gi, idx, U, erow, t, T, ej, nix, pgr, pgz, pgn);
   };
   gi_load(0);
 
@@ -638,7 +663,8 @@ hipError_t fv_gru_fwd_mfma(const float* gi, const void* whh_bf,
   if (H != 64) return hipErrorInvalidValue;
   dim3 grid((N + GM_S - 1) / GM_S);
   hipLaunchKernelGGL(gru_fwd_mfma_kernel<true>, grid, dim3(256), 0, stream,
-                     gi, whh_bf, bhh, h_final, h_seq, h_prev, gates4, N, T);
+                     gi, whh_bf, bhh, h_final, h_seq, h_prev, gates4, N, T,
+                     nullptr, 0);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -650,7 +676,8 @@ hipError_t fv_gru_fwd_mfma_f32(const float* gi, const float* Whh,
   if (H != 64) return hipErrorInvalidValue;
   dim3 grid((N + GM_S - 1) / GM_S);
   hipLaunchKernelGGL(gru_fwd_mfma_f32_kernel<true>, grid, dim3(256), 0, stream,
-                     gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T);
+                     gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N, T,
+                     nullptr, 0);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -663,7 +690,7 @@ hipError_t fv_gru_fwd_mfma_infer(const float* gi, const void* whh_bf,
   dim3 grid((N + GM_S - 1) / GM_S);
   hipLaunchKernelGGL(gru_fwd_mfma_kernel<false>, grid, dim3(256), 0, stream,
                      gi, whh_bf, bhh, h_final, nullptr, nullptr, nullptr, N,
-                     T);
+                     T, nullptr, 0);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -676,7 +703,37 @@ hipError_t fv_gru_fwd_mfma_f32_infer(const float* gi, const float* Whh,
   dim3 grid((N + GM_S - 1) / GM_S);
   hipLaunchKernelGGL(gru_fwd_mfma_f32_kernel<false>, grid, dim3(256), 0,
                      stream, gi, Whh, bhh, h_final, nullptr, nullptr, nullptr,
-                     N, T);
+                     N, T, nullptr, 0);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_fwd_mfma_infer_gather(const float* gi_rows, int U,
+                                        const int* idx, const void* whh_bf,
+                                        const float* bhh, float* h_final,
+                                        int N, int T, int H,
+                                        hipStream_t stream) {
+  if (H != 64 || U < 0) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GM_S - 1) / GM_S);
+  hipLaunchKernelGGL((gru_fwd_mfma_kernel<false, true>), grid, dim3(256), 0,
+                     stream, gi_rows, whh_bf, bhh, h_final, nullptr, nullptr,
+                     nullptr, N, T, idx, U);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_fwd_mfma_f32_infer_gather(const float* gi_rows, int U,
+                                            const int* idx, const float* Whh,
+                                            const float* bhh, float* h_final,
+                                            int N, int T, int H,
+                                            hipStream_t stream) {
+  if (H != 64 || U < 0) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GM_S - 1) / GM_S);
+  hipLaunchKernelGGL((gru_fwd_mfma_f32_kernel<false, true>), grid, dim3(256),
+                     0, stream, gi_rows, Whh, bhh, h_final, nullptr, nullptr,
+                     nullptr, N, T, idx, U);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "gru_gather.h"
 #include "launchers.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -65,8 +66,9 @@ DEVINL void wave_lds_order_() {
 #define GW_BA 8   // backward: 8 of 48 b128 reads ahead (32 registers)
 
 // SAVE=false (inference): no h_seq / h_prev / gates4 stores; the pointers
-// may be null.
-template <bool SAVE>
+// may be null. GATHER (gru_gather.h): gi is (U,192) and step t of stock s
+// reads row idx[s*T + t] of it; without it idx and U are not looked at.
+template <bool SAVE, bool GATHER = false>
 __global__ __launch_bounds__(256) void gru_fwd_wave_f32_kernel(
     const float* __restrict__ gi,      // (N,T,192)
     const float* __restrict__ Whh,     // (192,64)
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void gru_fwd_wave_f32_kernel(
     float* __restrict__ h_seq,         // (N,T,64) optional
     float* __restrict__ h_prev_out,    // (N,T,64)
     float* __restrict__ gates4,        // (N,T,256)
-    int N, int T) {
+    int N, int T, const int* __restrict__ idx, int U) {
   __shared__ __attribute__((aligned(16))) float wS[192 * GW_WS];
   __shared__ __attribute__((aligned(16))) float hS[GW_WPB][64];
 
@@ -124,17 +126,31 @@ __global__ __launch_bounds__(256) void gru_fwd_wave_f32_kernel(
   const float bh_n = bhh[128 + lane];
 
   const long row = (long)s * T;
-  const float* g0 = gi + row * 192;
-  float pgr = g0[lane], pgz = g0[64 + lane], pgn = g0[128 + lane];
+  float pgr, pgz, pgn;
+  WaveIdx wi;
+  if (GATHER) {
+    wi.init(idx + row, T, lane);
+    gather3_(gi, wi.at(0, lane), U, 64, lane, pgr, pgz, pgn);
+  } else {
+    const float* g0 = gi + row * 192;
+    pgr = g0[lane], pgz = g0[64 + lane], pgn = g0[128 + lane];
+  }
   float hp = 0.0f;
 
   for (int t = 0; t < T; ++t) {
     // next time step's gi, in flight across the chains and the gate math
-    // (the last step loads its own row again: no branch in the loop body)
-    const float* gx = gi + (row + (t + 1 < T ? t + 1 : t)) * 192;
-    const float xgr = gx[lane];
-    const float xgz = gx[64 + lane];
-    const float xgn = gx[128 + lane];
+    // (the last step loads its own row again: no branch in the loop body;
+    // the gather form, which branches on a missing row anyway, loads none)
+    float xgr, xgz, xgn;
+    if (GATHER) {
+      gather3_(gi, t + 1 < T ? wi.at(t + 1, lane) : -1, U, 64, lane, xgr,
+               xgz, xgn);
+    } else {
+      const float* gx = gi + (row + (t + 1 < T ? t + 1 : t)) * 192;
+      xgr = gx[lane];
+      xgz = gx[64 + lane];
+      xgn = gx[128 + lane];
+    }
 
     float ar = 0.0f, az = 0.0f, an = 0.0f;
 #pragma unroll
@@ -281,7 +297,7 @@ hipError_t fv_gru_fwd_wave_f32(const float* gi, const float* Whh,
   dim3 grid((N + GW_WPB - 1) / GW_WPB);
   hipLaunchKernelGGL(gru_fwd_wave_f32_kernel<true>, grid, dim3(256), 0,
                      stream, gi, Whh, bhh, h_final, h_seq, h_prev, gates4, N,
-                     T);
+                     T, nullptr, 0);
   HIP_CHECK_LAST();
   return hipSuccess;
 }
@@ -294,7 +310,22 @@ hipError_t fv_gru_fwd_wave_f32_infer(const float* gi, const float* Whh,
   dim3 grid((N + GW_WPB - 1) / GW_WPB);
   hipLaunchKernelGGL(gru_fwd_wave_f32_kernel<false>, grid, dim3(256), 0,
                      stream, gi, Whh, bhh, h_final, nullptr, nullptr, nullptr,
-                     N, T);
+                     N, T, nullptr, 0);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_fwd_wave_f32_infer_gather(const float* gi_rows, int U,
+                                            const int* idx, const float* Whh,
+                                            const float* bhh, float* h_final,
+                                            int N, int T, int H,
+                                            hipStream_t stream) {
+  if (H != 64 || U < 0) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GW_WPB - 1) / GW_WPB);
+  hipLaunchKernelGGL((gru_fwd_wave_f32_kernel<false, true>), grid, dim3(256),
+                     0, stream, gi_rows, Whh, bhh, h_final, nullptr, nullptr,
+                     nullptr, N, T, idx, U);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -152,6 +152,14 @@ hipError_t fv_gru_bwd(const float* dh_final, const float* h_prev,
                       const float* gates4, const float* Whh, float* dgi,
                       float* dgh, void* dgi_bf, void* dgh_bf, int N, int T,
                       int H, int variant, hipStream_t stream);
+// The gather forms of the inference recurrences (gru_gather.h): gi_rows is
+// (U,3H), idx (N,T) int32, and step t of stock n reads row idx[n*T + t]; an
+// index outside [0,U) reads nothing and makes that stock's h_final NaN.
+hipError_t fv_gru_fwd_infer_gather(const float* gi_rows, int U,
+                                   const int* idx, const float* Whh,
+                                   const float* bhh, float* h_final, int N,
+                                   int T, int H, int variant,
+                                   hipStream_t stream);
 
 // ---- gru_wave.hip -----------------------------------------------------
 // largest N at which fv_gru_fwd / _infer / _bwd take the wave kernels
@@ -163,6 +171,11 @@ hipError_t fv_gru_fwd_wave_f32(const float* gi, const float* Whh,
 hipError_t fv_gru_fwd_wave_f32_infer(const float* gi, const float* Whh,
                                      const float* bhh, float* h_final, int N,
                                      int T, int H, hipStream_t stream);
+hipError_t fv_gru_fwd_wave_f32_infer_gather(const float* gi_rows, int U,
+                                            const int* idx, const float* Whh,
+                                            const float* bhh, float* h_final,
+                                            int N, int T, int H,
+                                            hipStream_t stream);
 hipError_t fv_gru_bwd_wave_f32(const float* dh_final, const float* h_prev,
                                const float* gates4, const float* Whh,
                                float* dgi, float* dgh, int N, int T, int H,
@@ -185,6 +198,16 @@ hipError_t fv_gru_fwd_mfma_infer(const float* gi, const void* whh_bf,
 hipError_t fv_gru_fwd_mfma_f32_infer(const float* gi, const float* Whh,
                                      const float* bhh, float* h_final, int N,
                                      int T, int H, hipStream_t stream);
+hipError_t fv_gru_fwd_mfma_infer_gather(const float* gi_rows, int U,
+                                        const int* idx, const void* whh_bf,
+                                        const float* bhh, float* h_final,
+                                        int N, int T, int H,
+                                        hipStream_t stream);
+hipError_t fv_gru_fwd_mfma_f32_infer_gather(const float* gi_rows, int U,
+                                            const int* idx, const float* Whh,
+                                            const float* bhh, float* h_final,
+                                            int N, int T, int H,
+                                            hipStream_t stream);
 hipError_t fv_gru_bwd_mfma_f32(const float* dh_final, const float* h_prev,
                                const float* gates4, const float* Whh,
                                float* dgi, float* dgh, int N, int T, int H,

@@ -21,6 +21,7 @@ import pandas as pd
 import torch
 
 from .backtest import BacktestConfig, backtest_report, topk_dropout_backtest
+from .data.panel import PanelDays
 from .data.sampler import init_data_loader
 from .utils import RankIC, generate_prediction_scores, load_model, test_args
 
@@ -73,30 +74,47 @@ def build_argparser() -> argparse.ArgumentParser:
                         "(<stem>_factors.csv) and its validation loss terms "
                         "(<stem>_daily.csv) next to the score CSV; decoder "
                         "noise off, so the files are reproducible")
+    p.add_argument("--panel", action="store_true",
+                   help="hold the range once per (stock, date) row and send "
+                        "the scores, --dist, --metrics and --factors through "
+                        "the panel route (faster on the fused engine, the "
+                        "same files on the eager one)")
     p.add_argument("--topk", type=int, default=50)
     p.add_argument("--n_drop", type=int, default=10)
     return p
 
 
+def _panel_windows(panel):
+    """The days of a PanelDays as the eager code takes them."""
+    return [panel.windows(d) for d in range(len(panel))]
+
+
 def range_metrics(model, loader, seq_length: int, engine: str = "auto",
-                  topk: int = 50):
+                  topk: int = 50, panel: bool = False):
     """Summary of the loader's days ranked on the predictive mean: the
     fused engine's on-device evaluation on a GPU (engine "auto"/"fused"),
-    metrics.py's oracle on the eager module otherwise."""
+    metrics.py's oracle on the eager module otherwise. panel=True takes
+    the days as a PanelDays (the fused engine's panel route; the eager
+    engine evaluates its windows())."""
+    from .engine.trainer import resolve_engine
     from .metrics import evaluate_days_eager, summarize_ic
 
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.to(device)
-    days = []
-    for char_with_label, _ in loader:
-        if char_with_label.shape[1] != seq_length:
-            continue
-        days.append((char_with_label[:, :, :-1].float(),
-                     char_with_label[:, -1, -1].float()))
-    from .engine.trainer import resolve_engine
-
     hidden = model.feature_extractor.gru.hidden_size
-    if resolve_engine(engine, hidden, device.type, warn=False) == "fused":
+    fused = resolve_engine(engine, hidden, device.type, warn=False) == "fused"
+    if panel:
+        days = PanelDays.from_loader(loader)
+        if not fused:
+            days = _panel_windows(days)
+    else:
+        days = []
+        for char_with_label, _ in loader:
+            if char_with_label.shape[1] != seq_length:
+                continue
+            days.append((char_with_label[:, :, :-1].float(),
+                         char_with_label[:, -1, -1].float()))
+    if fused:
         from .engine.fused import FusedTrainer
 
         trainer = FusedTrainer(model, lr=0.0, t_max=1, device=device,
@@ -106,7 +124,8 @@ def range_metrics(model, loader, seq_length: int, engine: str = "auto",
                                             topk=topk))
 
 
-def range_factors(model, loader, seq_length: int, engine: str = "auto"):
+def range_factors(model, loader, seq_length: int, engine: str = "auto",
+                  panel: bool = False):
     """The factors and the validation loss of every day of the loader, with
     the decoder noise off (the reconstruction is the posterior mean), so
     the result is reproducible: (factors, daily) DataFrames —
@@ -117,23 +136,33 @@ def range_factors(model, loader, seq_length: int, engine: str = "auto"):
     The fused engine's loss_many on a GPU (engine "auto"/"fused"),
     metrics.loss_days_eager on the eager module otherwise. Dates come from
     the dataset's (datetime, instrument) index, walked in loader order as
-    generate_prediction_scores does."""
+    generate_prediction_scores does. panel=True takes days and dates from
+    a PanelDays (the fused engine's panel route; the eager engine works on
+    its windows())."""
     from .engine.trainer import resolve_engine
     from .metrics import FACTOR_KEYS, loss_days_eager
 
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.to(device)
-    index = loader.dataset.get_index()
-    days, dates, row = [], [], 0
-    for char_with_label, _ in loader:
-        n = int(char_with_label.shape[0])
-        if char_with_label.shape[1] == seq_length and n > 0:
-            days.append((char_with_label[:, :, :-1].float(),
-                         char_with_label[:, -1, -1].float()))
-            dates.append(index[row][0])
-        row += n
     hidden = model.feature_extractor.gru.hidden_size
-    if resolve_engine(engine, hidden, device.type, warn=False) == "fused":
+    fused = resolve_engine(engine, hidden, device.type, warn=False) == "fused"
+    if panel:
+        # a loader day always has rows, so none is left out here either
+        days = PanelDays.from_loader(loader)
+        dates = days.dates
+        if not fused:
+            days = _panel_windows(days)
+    else:
+        index = loader.dataset.get_index()
+        days, dates, row = [], [], 0
+        for char_with_label, _ in loader:
+            n = int(char_with_label.shape[0])
+            if char_with_label.shape[1] == seq_length and n > 0:
+                days.append((char_with_label[:, :, :-1].float(),
+                             char_with_label[:, -1, -1].float()))
+                dates.append(index[row][0])
+            row += n
+    if fused:
         from .engine.fused import FusedTrainer
 
         trainer = FusedTrainer(model, lr=0.0, t_max=1, device=device,
@@ -172,7 +201,8 @@ def main(argv=None):
                                         targs, engine=args.engine,
                                         batch_days=args.batch_days,
                                         return_dist=args.dist,
-                                        risk_aversion=args.risk_aversion)
+                                        risk_aversion=args.risk_aversion,
+                                        panel=args.panel)
 
     os.makedirs(args.out_dir, exist_ok=True)
     # reference artifact name schema (scores/readme.md)
@@ -184,7 +214,8 @@ def main(argv=None):
 
     if args.metrics:
         summary = range_metrics(model, loader, args.seq_length,
-                                engine=args.engine, topk=args.metrics_topk)
+                                engine=args.engine, topk=args.metrics_topk,
+                                panel=args.panel)
         print("\nmetrics on mu:")
         for k in ("IC", "ICIR", "RankIC", "RankIC_IR", "long_short",
                   "n_days"):
@@ -196,7 +227,7 @@ def main(argv=None):
 
     if args.factors:
         factors, daily = range_factors(model, loader, args.seq_length,
-                                       engine=args.engine)
+                                       engine=args.engine, panel=args.panel)
         stem = os.path.splitext(out_csv)[0]
         factors.to_csv(stem + "_factors.csv", index=False)
         daily.to_csv(stem + "_daily.csv", index=False)

@@ -90,7 +90,8 @@ def checkpoint_path(save_dir: str, run_name: str, num_factor: int,
 def generate_prediction_scores(model, test_dataloader, test_dataset, args,
                                engine: str = "auto", batch_days: int = 1,
                                return_dist: bool = False,
-                               risk_aversion: float = 0.0):
+                               risk_aversion: float = 0.0,
+                               panel: bool = False):
     """Score every test cross-section with model.prediction; returns a
     MultiIndex (datetime, instrument) DataFrame['score'].
 
@@ -108,7 +109,10 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
     return_dist adds the decoder's predictive mean and risk as `mu` and
     `sigma` columns; risk_aversion = eta != 0 makes `score` the
     deterministic risk-adjusted mu - eta * sigma (and implies
-    return_dist)."""
+    return_dist); panel=True takes the days as a data.panel.PanelDays
+    built from the loader's sampler: the fused engine scores it in one
+    predict_many call (the extractor head once per (stock, date) row),
+    the eager engine scores its windows(), which are the loader's days."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.to(device)
     model.eval()
@@ -127,7 +131,7 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
         except Exception:
             trainer = None
 
-    if batch_days == 1 and not want_dist:
+    if batch_days == 1 and not want_dist and not panel:
         for char_with_label, _ in test_dataloader:
             if char_with_label.shape[1] != args.seq_length:
                 continue
@@ -140,7 +144,7 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
         cols = ["score"]
     else:
         def flush(days):
-            if not days:
+            if not len(days):
                 return
             if trainer is not None:
                 outs = trainer.predict_many(days, return_dist=want_dist)
@@ -163,15 +167,23 @@ def generate_prediction_scores(model, test_dataloader, test_dataset, args,
                 else:
                     ls.append(o.detach().cpu())
 
-        pending = []
-        for char_with_label, _ in test_dataloader:
-            if char_with_label.shape[1] != args.seq_length:
-                continue
-            pending.append(char_with_label[:, :, :-1].float())
-            if len(pending) == batch_days:
-                flush(pending)
-                pending = []
-        flush(pending)
+        if panel:
+            from .data.panel import PanelDays
+
+            days = PanelDays.from_loader(test_dataloader)
+            if trainer is None:
+                days = [days.windows(d)[0] for d in range(len(days))]
+            flush(days)
+        else:
+            pending = []
+            for char_with_label, _ in test_dataloader:
+                if char_with_label.shape[1] != args.seq_length:
+                    continue
+                pending.append(char_with_label[:, :, :-1].float())
+                if len(pending) == batch_days:
+                    flush(pending)
+                    pending = []
+            flush(pending)
         cols = ["score", "mu", "sigma"] if want_dist else ["score"]
 
     ls = torch.cat(ls, dim=0)

@@ -1543,7 +1543,8 @@ class FusedTrainer:
     # ~2 KB of workspace per row at C=158/H=64, i.e. about 1 GB
     PREDICT_ROWS = 1 << 19
 
-    def _alloc_infer_ws(self, R: int, Nn: int, D: int, with_beta: bool):
+    def _alloc_infer_ws(self, R: int, Nn: int, D: int, with_beta: bool,
+                        with_svar: bool = False):
         """Grow-only inference workspace of predict_many; separate from
         self.ws / the (N, T) shape cache so scoring never disturbs
         training buffers or captured graphs."""
@@ -1580,10 +1581,13 @@ class FusedTrainer:
             iw["eps"] = f(Nn)
             iw["out"] = f(3, Nn)  # rows: sample, mu, sigma
             iw.pop("beta", None)
+            iw.pop("svar", None)
             iw.pop("label", None)
             iw["N"] = Nn
         if with_beta and "beta" not in iw:
             iw["beta"] = f(iw["N"], K)
+        if with_svar and "svar" not in iw:
+            iw["svar"] = f(iw["N"])
         if D > iw["D"]:
             iw["seg_off"] = torch.empty(D + 1, device=d, dtype=torch.int32)
             iw["pmu"] = f(D, K)
@@ -1623,7 +1627,8 @@ class FusedTrainer:
 
     def _launch_predict_many(self, iw, R: int, Nn: int, D: int, T: int,
                              max_n: int, with_beta: bool,
-                             prior_dec: bool = True):
+                             prior_dec: bool = True,
+                             with_svar: bool = False):
         """Kernel sequence of one packed chunk: extractor head of the
         engine's dtype over all rows -> GRU without backward state ->
         _launch_pm_tail."""
@@ -1636,13 +1641,16 @@ class FusedTrainer:
         else:
             ext.gru_fwd_infer(gi, p("Whh"), p("bhh"), h, Nn, T, H,
                               variant=self._gru_v)
-        self._launch_pm_tail(iw, Nn, D, max_n, with_beta, prior_dec)
+        self._launch_pm_tail(iw, Nn, D, max_n, with_beta, prior_dec,
+                             with_svar)
 
     def _launch_pm_tail(self, iw, Nn: int, D: int, max_n: int,
-                        with_beta: bool, prior_dec: bool = True):
+                        with_beta: bool, prior_dec: bool = True,
+                        with_svar: bool = False):
         """Behind the GRU of one packed chunk: segmented prior attention ->
         segmented decoder (prior_dec=False stops behind the attention:
-        loss_many decodes the posterior only)."""
+        loss_many decodes the posterior only). with_svar: the decoder also
+        writes the rows' idiosyncratic variance into iw["svar"]."""
         ext, p, H = self.ext, self.p, self.H
         h = iw["h"][:Nn]
         seg = iw["seg_off"][:D + 1]
@@ -1658,7 +1666,8 @@ class FusedTrainer:
                         p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"), iw["pmu"],
                         iw["psig_c"], iw["eps"][:Nn], out[1, :Nn],
                         out[2, :Nn], out[0, :Nn],
-                        iw["beta"][:Nn] if with_beta else None)
+                        iw["beta"][:Nn] if with_beta else None,
+                        iw["svar"][:Nn] if with_svar else None)
 
     def _launch_posterior(self, iw, Nn: int, D: int, max_n: int,
                           with_factors: bool):
@@ -1816,8 +1825,166 @@ class FusedTrainer:
                                             return_beta)
         return results
 
+    @torch.no_grad()
+    def risk_many(self, xs, weights=None, solve=(),
+                  return_components: bool = False,
+                  max_rows: Optional[int] = None):
+        """The factor risk model of many trading days on the device: per
+        day the covariance the prior decoder implies,
+        Sigma = beta diag(factor_sigma^2) beta^T + diag(specific_var)
+        (factorvae_amd.risk), evaluated for one portfolio and optionally
+        solved for minimum-variance / mean-variance weights, without beta
+        or Sigma leaving the device.
+
+        xs: list of (N_d, T, C) or a PanelDays, as for predict_many.
+        weights: None (equal weight 1/N_d) or one (N_d,) tensor per day,
+        host or device, used as given (no normalisation). solve: a subset
+        of ("minvar", "mv"): Sigma^-1 1 / (1^T Sigma^-1 1) and
+        Sigma^-1 mu / |Sigma^-1 mu|_1 (all-zero when that norm is 0).
+
+        Returns host tensors in input-day order: "n" (D,) int32; "mean",
+        "mean_factor", "var_factor", "var_specific", "vol" (D,) float32;
+        "exposure", "factor_var" (D, K); "mcr" a list of (N_d,) marginal
+        contributions to risk (sum_i w_i mcr_i = vol); with solve the
+        lists "minvar" / "mv" of (N_d,) weights and "solve_info" (D,)
+        int32 (0 solved, 1 a failed Cholesky pivot: that day's weights are
+        NaN); with return_components the lists "mu", "specific_var"
+        (N_d,), "beta" (N_d, K) and "factor_mu", "factor_sigma" (D, K). A
+        day without rows has n = 0, NaN per-day values and empty per-stock
+        tensors.
+
+        Days are chunked exactly as in predict_many (one kernel sequence
+        and one device-to-host copy of a flat result buffer per chunk) and
+        a day's result does not depend on what it is batched with. The
+        decoder's eps is zero-filled: torch's generators are left alone.
+        Like predict_many it touches no training buffer or captured
+        graph."""
+        from ..risk import STAT_KEYS, check_solve, check_weights, empty_result
+
+        solve = check_solve(solve)
+        panel = isinstance(xs, PanelDays)
+        if not panel:
+            xs = list(xs)
+        lens_all = xs.lens() if panel else [int(x.shape[0]) for x in xs]
+        weights = check_weights(weights, lens_all)
+        K, R, dev = self.K, len(solve), self.device
+        res = empty_result(lens_all, K, solve, return_components)
+        for idxs, lens, offs, iw in self._pm_chunks(
+                "risk_many", xs, None, max_rows, True, draw_eps=False,
+                with_svar=True):
+            if iw is None:
+                continue  # days without rows: n = 0, NaN
+            D, Nn = len(idxs), offs[-1]
+            # flat result: stats D*5 | exposure D*K | factor_var D*K |
+            # mcr Nn | weights Nn*R | info D (int32 bits) | components
+            size = D * (5 + 2 * K) + Nn + Nn * R + (D if R else 0)
+            if return_components:
+                size += Nn * (2 + K) + 2 * D * K
+            if iw.get("risk_cap", 0) < size:
+                iw["risk"] = torch.empty(size, device=dev)
+                iw["risk_cap"] = size
+            if iw.get("risk_w_cap", 0) < iw["N"]:
+                iw["risk_w"] = torch.empty(iw["N"], device=dev)
+                iw["risk_b"] = torch.empty(iw["N"] * 4, device=dev)
+                iw["risk_x"] = torch.empty(iw["N"] * 4, device=dev)
+                iw["risk_w_cap"] = iw["N"]
+            flat, o = iw["risk"], 0
+
+            def take(n, *shape):
+                nonlocal o
+                v = flat[o:o + n]
+                o += n
+                return v.view(*shape) if shape else v
+
+            stats = take(D * 5, D, 5)
+            expo, fvar = take(D * K, D, K), take(D * K, D, K)
+            mcr = take(Nn)
+            wout = take(Nn * R, R, Nn) if R else None
+            info = take(D).view(torch.int32) if R else None
+
+            wd = iw["risk_w"]
+            if weights is None:
+                wd[:Nn].copy_(torch.cat([
+                    torch.full((n,), 1.0 / n if n else 0.0) for n in lens]))
+            else:
+                self._pm_pack_rows(wd, [weights[i] for i in idxs], offs,
+                                   lens)
+            seg = iw["seg_off"][:D + 1]
+            beta, svar = iw["beta"][:Nn], iw["svar"][:Nn]
+            mu = iw["out"][1, :Nn]
+            pmu, psig_c = iw["pmu"][:D], iw["psig_c"][:D]
+            self.ext.risk_seg(beta, svar, mu, wd[:Nn], seg, pmu, psig_c,
+                              stats, expo, fvar, mcr)
+            if R:
+                b = iw["risk_b"][:Nn * R].view(Nn, R)
+                x = iw["risk_x"][:Nn * R].view(Nn, R)
+                for c, s in enumerate(solve):
+                    if s == "minvar":
+                        b[:, c].fill_(1.0)
+                    else:
+                        b[:, c].copy_(mu)
+                norms = torch.empty(D, 2, R, device=dev)
+                self.ext.risk_solve_seg(beta, svar, seg, psig_c, b, x, info,
+                                        norms)
+                # the day's normaliser spread over its rows; the segment
+                # sums come from the kernel, ordered within the day
+                rows = torch.repeat_interleave(
+                    norms, torch.tensor(lens, device=dev), dim=0,
+                    output_size=Nn)
+                for c, s in enumerate(solve):
+                    if s == "minvar":
+                        torch.div(x[:, c], rows[:, 0, c], out=wout[c])
+                    else:
+                        den = rows[:, 1, c]
+                        wout[c].copy_(torch.where(
+                            den == 0, torch.zeros_like(den), x[:, c] / den))
+            if return_components:
+                take(Nn).copy_(mu)
+                take(Nn).copy_(svar)
+                take(Nn * K).copy_(beta.reshape(-1))
+                take(D * K).copy_(pmu.reshape(-1))
+                take(D * K).copy_(psig_c.reshape(-1))
+            host = flat[:o].cpu()  # the chunk's one D2H copy
+            o = 0
+
+            def give(n, *shape):
+                nonlocal o
+                v = host[o:o + n]
+                o += n
+                return v.view(*shape) if shape else v
+
+            ii = torch.tensor(idxs)
+            st_h = give(D * 5, D, 5)
+            for j, k in enumerate(STAT_KEYS):
+                res[k][ii] = st_h[:, j]
+            res["exposure"][ii] = give(D * K, D, K)
+            res["factor_var"][ii] = give(D * K, D, K)
+            per_stock = {"mcr": give(Nn)}
+            if R:
+                w_h = give(Nn * R, R, Nn)
+                for c, s in enumerate(solve):
+                    per_stock[s] = w_h[c]
+                res["solve_info"][ii] = give(D).view(torch.int32)
+            if return_components:
+                per_stock["mu"] = give(Nn)
+                per_stock["specific_var"] = give(Nn)
+                per_stock["beta"] = give(Nn * K, Nn, K)
+                res["factor_mu"][ii] = give(D * K, D, K)
+                res["factor_sigma"][ii] = give(D * K, D, K)
+            for k, v in per_stock.items():
+                for i, a, n in zip(idxs, offs, lens):
+                    res[k][i] = v[a:a + n]
+        if return_components:
+            # an empty day inside a chunk: its prior rows were never
+            # written on the device
+            empty = res["n"] == 0
+            res["factor_mu"][empty] = float("nan")
+            res["factor_sigma"][empty] = float("nan")
+        return res
+
     def _pm_chunks(self, what: str, xs, eps, max_rows, with_beta: bool,
-                   ys=None, draw_eps: bool = True, prior_dec: bool = True):
+                   ys=None, draw_eps: bool = True, prior_dec: bool = True,
+                   with_svar: bool = False):
         """The chunk/pack loop shared by predict_many and evaluate_many:
         checks the days, packs them greedily into chunks within max_rows,
         and for each chunk copies the inputs into the inference workspace,
@@ -1826,7 +1993,8 @@ class FusedTrainer:
         iw = None and launches nothing. ys: optional per-day labels, packed
         into iw["label"]. draw_eps=False zero-fills a missing eps instead
         of drawing it, leaving torch's generator alone. prior_dec=False
-        leaves out the prior decoder (_launch_predict_many). xs may be a
+        leaves out the prior decoder (_launch_predict_many); with_svar
+        adds its idiosyncratic variance output iw["svar"]. xs may be a
         PanelDays (_pm_chunks_panel): the same chunks, the same yields."""
         if self.fp8:
             raise ValueError(f"{what} supports the fp32 and bf16 "
@@ -1842,7 +2010,7 @@ class FusedTrainer:
         if isinstance(xs, PanelDays):
             yield from self._pm_chunks_panel(what, xs, eps, max_rows,
                                              with_beta, ys, draw_eps,
-                                             prior_dec)
+                                             prior_dec, with_svar)
             return
         T = xs[0].shape[1]
         for i, x in enumerate(xs):
@@ -1876,7 +2044,7 @@ class FusedTrainer:
             if Nn == 0:
                 yield idxs, lens, offs, None
                 continue
-            iw = self._alloc_infer_ws(R, Nn, D, with_beta)
+            iw = self._alloc_infer_ws(R, Nn, D, with_beta, with_svar)
             if not qk_done:
                 ext.attn_qk_fwd(self.p_q, self.p_Wk, self.p_bk, iw["qk"],
                                 iw["cb"])
@@ -1896,7 +2064,7 @@ class FusedTrainer:
                     xd[o * T:(o + n) * T].copy_(t)
             self._pm_pack_eps_labels(iw, idxs, lens, offs, eps, ys, draw_eps)
             self._launch_predict_many(iw, R, Nn, D, T, max(lens), with_beta,
-                                      prior_dec)
+                                      prior_dec, with_svar)
             yield idxs, lens, offs, iw
 
     @staticmethod
@@ -1949,7 +2117,7 @@ class FusedTrainer:
 
     def _pm_chunks_panel(self, what: str, panel, eps, max_rows,
                          with_beta: bool, ys, draw_eps: bool,
-                         prior_dec: bool):
+                         prior_dec: bool, with_svar: bool = False):
         """_pm_chunks for a PanelDays: the same greedy day chunks (so a
         seed draws the same eps) and the same yields, but the extractor
         head runs once per referenced row and the GRU gathers.
@@ -2011,7 +2179,7 @@ class FusedTrainer:
                 continue
             iw = self._alloc_infer_ws(min(step, max(U, 1)), Nn_max,
                                       max(len(idxs) for idxs in chunks),
-                                      with_beta)
+                                      with_beta, with_svar)
             if iw.get("gi_rows_cap", 0) < max(U, 1):
                 iw["gi_rows"] = torch.empty(max(U, 1), 3 * H, device=dev)
                 iw["gi_rows_cap"] = max(U, 1)
@@ -2057,7 +2225,7 @@ class FusedTrainer:
                                              p("bhh"), h, Nn, T, H,
                                              variant=self._gru_v)
                 self._launch_pm_tail(iw, Nn, D, max(cl), with_beta,
-                                     prior_dec)
+                                     prior_dec, with_svar)
                 yield idxs, cl, offs, iw
 
     @staticmethod

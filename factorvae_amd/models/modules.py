@@ -349,6 +349,27 @@ class FactorVAE(nn.Module):
         pred_mu, pred_sigma = self.factor_predictor(stock_latent)
         return self.factor_decoder.dist(stock_latent, pred_mu, pred_sigma)
 
+    @torch.no_grad()
+    def risk_model(self, x: torch.Tensor):
+        """Components of the covariance the prior decoder implies for the
+        day x (N, T, C): Sigma = beta diag(factor_sigma^2) beta^T +
+        diag(specific_var), whose diagonal is prediction_dist's sigma^2.
+        A dict with mu (N,), beta (N, K), specific_var (N,) =
+        alpha_sigma^2 + 1e-6, factor_mu (K,) and factor_sigma (K,) after
+        the decoder's zero clamp; factorvae_amd.risk works on it. Beyond
+        the reference."""
+        stock_latent = self.feature_extractor(x)
+        factor_mu, factor_sigma = self.factor_predictor(stock_latent)
+        factor_sigma = torch.where(
+            factor_sigma == 0, torch.full_like(factor_sigma, 1e-6),
+            factor_sigma)
+        alpha_mu, alpha_sigma = self.factor_decoder.alpha_layer(stock_latent)
+        beta = self.factor_decoder.beta_layer(stock_latent)
+        mu = alpha_mu.view(-1) + torch.matmul(beta, factor_mu)
+        return {"mu": mu, "beta": beta,
+                "specific_var": alpha_sigma.view(-1) ** 2 + 1e-6,
+                "factor_mu": factor_mu, "factor_sigma": factor_sigma}
+
 
 def build_factorvae(num_latent: int = 158, hidden_size: int = 64,
                     num_portfolio: int = 128, num_factor: int = 96) -> FactorVAE:

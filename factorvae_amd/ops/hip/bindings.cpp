@@ -1134,11 +1134,13 @@ void attn_seg_fwd(Tensor h, Tensor seg_off, long max_n, Tensor qk, Tensor cb,
 }
 
 // fmu / fsig_c are (D,K): each row takes its own day's factor prior.
-// eps/sample and beta are optional; sample = fma(eps, sigma, mu).
+// eps/sample, beta and svar are optional; sample = fma(eps, sigma, mu),
+// svar (N) = alpha_sigma^2 + 1e-6, the row's idiosyncratic variance.
 void dec_seg_fwd(Tensor h, Tensor seg_off, Tensor W1, Tensor b1, Tensor wmu,
                  Tensor bmu, Tensor wsig, Tensor bsig, Tensor Wb, Tensor bb,
                  Tensor fmu, Tensor fsig_c, OptTensor eps, Tensor mu,
-                 Tensor sigma, OptTensor sample, OptTensor beta) {
+                 Tensor sigma, OptTensor sample, OptTensor beta,
+                 OptTensor svar) {
   OP("dec_seg_fwd", h);
   op.require(h.dim() == 2 && Wb.dim() == 2 && Wb.size(1) == h.size(1),
              "want h (N,H), Wb (K,H)");
@@ -1154,7 +1156,52 @@ void dec_seg_fwd(Tensor h, Tensor seg_off, Tensor W1, Tensor b1, Tensor wmu,
       P_F32(bsig, 1), P_F32_EQ(Wb, K * H), P_F32_EQ(bb, K),
       P_F32(fmu, D * K), P_F32(fsig_c, D * K), ep, P_F32(mu, N),
       P_F32(sigma, N), ep ? P_F32(sample, N) : nullptr, P_F32(beta, N * K),
-      N, D, K, H, cur_stream()));
+      P_F32(svar, N), N, D, K, H, cur_stream()));
+}
+
+// ---- factor risk model ----------------------------------------------
+// beta (total,K), svar / mu / w (total) packed days, seg_off int32 (D+1),
+// pmu / psig_c (D,K). Outputs: stats (D,5) = mean, mean_factor,
+// var_factor, var_specific, vol; exposure, factor_var (D,K); mcr (total).
+// A day without rows gets NaN in its per-day rows.
+void risk_seg(Tensor beta, Tensor svar, Tensor mu, Tensor w, Tensor seg_off,
+              Tensor pmu, Tensor psig_c, Tensor stats, Tensor exposure,
+              Tensor factor_var, Tensor mcr) {
+  OP("risk_seg", beta);
+  op.require(beta.dim() == 2 && pmu.dim() == 2 &&
+                 pmu.size(1) == beta.size(1),
+             "want beta (total,K), pmu (D,K)");
+  const long total = DIM(beta, 0), K = DIM(beta, 1), D = DIM(pmu, 0);
+  op.require(K >= 1 && K <= 128, "supports 1 <= K <= 128, got K=", K);
+  RUN(fv_risk_seg(P_F32(beta, total * K), P_F32(svar, total),
+                  P_F32(mu, total), P_F32(w, total), P_I32(seg_off, D + 1),
+                  P_F32(pmu, D * K), P_F32(psig_c, D * K),
+                  P_F32(stats, D * 5), P_F32(exposure, D * K),
+                  P_F32(factor_var, D * K), P_F32(mcr, total), total, D, K,
+                  cur_stream()));
+}
+
+// x (total,R) = Sigma_d^-1 b for b (total,R), 1 <= R <= 4, through the
+// factor structure; info (D) int32: 0 solved, 1 failed pivot (the day's x
+// is NaN), 2 rows outside the packed buffer. psig_c (D,K) gives D. norms
+// (D,2,R), optional: the day's sum x and sum |x| per column.
+void risk_solve_seg(Tensor beta, Tensor svar, Tensor seg_off, Tensor psig_c,
+                    Tensor b, Tensor x, Tensor info,
+                    OptTensor norms) {
+  OP("risk_solve_seg", beta);
+  op.require(beta.dim() == 2 && psig_c.dim() == 2 &&
+                 psig_c.size(1) == beta.size(1),
+             "want beta (total,K), psig_c (D,K)");
+  const long total = DIM(beta, 0), K = DIM(beta, 1), D = DIM(psig_c, 0);
+  op.require(b.dim() == 2 && b.size(0) == total, "b must be (total,R)");
+  const long R = DIM(b, 1);
+  op.require(K >= 1 && K <= 128, "supports 1 <= K <= 128, got K=", K);
+  op.require(R >= 1 && R <= 4, "supports 1 <= R <= 4, got R=", R);
+  RUN(fv_risk_solve_seg(P_F32(beta, total * K), P_F32(svar, total),
+                        P_I32(seg_off, D + 1), P_F32(psig_c, D * K),
+                        P_F32(b, total * R), P_F32(x, total * R),
+                        P_I32(info, D), P_F32(norms, D * 2 * R), total, D, K,
+                        R, cur_stream()));
 }
 
 // ---- batched multi-day posterior pass ------------------------------
@@ -1433,7 +1480,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("wmu"), py::arg("bmu"), py::arg("wsig"), py::arg("bsig"),
           py::arg("Wb"), py::arg("bb"), py::arg("fmu"), py::arg("fsig_c"),
           py::arg("eps"), py::arg("mu"), py::arg("sigma"),
-          py::arg("sample") = py::none(), py::arg("beta") = py::none());
+          py::arg("sample") = py::none(), py::arg("beta") = py::none(),
+          py::arg("svar") = py::none());
+  // factor risk model of the prior decoder
+  mod.def("risk_seg", &risk_seg,
+          py::arg("beta"), py::arg("svar"), py::arg("mu"), py::arg("w"),
+          py::arg("seg_off"), py::arg("pmu"), py::arg("psig_c"),
+          py::arg("stats"), py::arg("exposure"), py::arg("factor_var"),
+          py::arg("mcr"));
+  mod.def("risk_solve_seg", &risk_solve_seg,
+          py::arg("beta"), py::arg("svar"), py::arg("seg_off"),
+          py::arg("psig_c"), py::arg("b"), py::arg("x"), py::arg("info"),
+          py::arg("norms") = py::none());
   // batched multi-day posterior pass (inference only)
   mod.def("enc_seg_fwd", &enc_seg_fwd,
           py::arg("h"), py::arg("seg_off"), py::arg("max_n"),

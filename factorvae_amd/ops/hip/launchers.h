@@ -378,8 +378,9 @@ hipError_t fv_dec_seg_fwd(const float* h, const int* seg_off, const float* W1,
                           const float* wsig, const float* bsig,
                           const float* Wb, const float* bb, const float* fmu,
                           const float* fsig_c, const float* eps, float* mu,
-                          float* sigma, float* sample, float* beta, int N,
-                          int D, int K, int H, hipStream_t s);
+                          float* sigma, float* sample, float* beta,
+                          float* svar, int N, int D, int K, int H,
+                          hipStream_t s);
 
 // ---- posterior.hip ----------------------------------------------------
 hipError_t fv_enc_seg_fwd(const float* h, const int* seg_off,
@@ -395,6 +396,18 @@ hipError_t fv_loss_seg(const float* recon, const float* y, const int* seg_off,
                        const float* pmu, const float* psig_c, float* loss,
                        float* mse, float* kl, int total, int D, int K,
                        hipStream_t s);
+
+// ---- risk.hip (factor risk model of the prior decoder) -----------------
+hipError_t fv_risk_seg(const float* beta, const float* svar, const float* mu,
+                       const float* w, const int* seg_off, const float* pmu,
+                       const float* psig_c, float* stats, float* exposure,
+                       float* factor_var, float* mcr, int total, int D, int K,
+                       hipStream_t s);
+hipError_t fv_risk_solve_seg(const float* beta, const float* svar,
+                             const int* seg_off, const float* psig_c,
+                             const float* b, float* x, int* info,
+                             float* norms, int total, int D, int K, int R,
+                             hipStream_t s);
 
 // ---- metrics.hip ------------------------------------------------------
 hipError_t fv_daily_ic_seg(const float* pred, long ld, const float* label,

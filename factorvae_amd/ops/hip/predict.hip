@@ -218,6 +218,7 @@ __global__ __launch_bounds__(256) void dec_seg_fwd_kernel(
     float* __restrict__ mu_out, float* __restrict__ sigma_out,
     float* __restrict__ sample_out,  // written only with eps
     float* __restrict__ beta_out,    // (sumN,K) or null
+    float* __restrict__ svar_out,    // (sumN) or null: asig^2 + 1e-6
     int N, int D, int K, int H, int iters) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* W1T = (float*)smem;                   // [H][H]
@@ -294,6 +295,10 @@ __global__ __launch_bounds__(256) void dec_seg_fwd_kernel(
       mu_out[row] = mu;
       sigma_out[row] = sig;
       if (eps) sample_out[row] = fmaf(eps[row], sig, mu);
+      // the row's idiosyncratic variance, from the same softplus; an
+      // explicit fmaf, so no multiply is shared with var above and its
+      // contraction (and sigma's bits) stay as they were
+      if (svar_out) svar_out[row] = fmaf(asig, asig, 1e-6f);
     }
   }
 }
@@ -338,8 +343,8 @@ hipError_t fv_dec_seg_fwd(const float* h, const int* seg_off,
                           const float* bsig, const float* Wb, const float* bb,
                           const float* fmu, const float* fsig_c,
                           const float* eps, float* mu, float* sigma,
-                          float* sample, float* beta, int N, int D, int K,
-                          int H, hipStream_t s) {
+                          float* sample, float* beta, float* svar, int N,
+                          int D, int K, int H, hipStream_t s) {
   if (H > 64 || K > 128) return hipErrorInvalidValue;
   if (N <= 0 || D <= 0) return hipSuccess;
   if (eps && !sample) return hipErrorInvalidValue;
@@ -353,7 +358,8 @@ hipError_t fv_dec_seg_fwd(const float* h, const int* seg_off,
   const int nblk = (N + DSEG_RPW * iters - 1) / (DSEG_RPW * iters);
   hipLaunchKernelGGL(dec_seg_fwd_kernel, dim3(nblk), dim3(256), lds, s, h,
                      seg_off, W1, b1, wmu, bmu, wsig, bsig, Wb, bb, fmu,
-                     fsig_c, eps, mu, sigma, sample, beta, N, D, K, H, iters);
+                     fsig_c, eps, mu, sigma, sample, beta, svar, N, D, K, H,
+                     iters);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -79,6 +79,19 @@ def build_argparser() -> argparse.ArgumentParser:
                         "the scores, --dist, --metrics and --factors through "
                         "the panel route (faster on the fused engine, the "
                         "same files on the eager one)")
+    p.add_argument("--risk", action="store_true",
+                   help="with --dist: also write the factor risk model's "
+                        "view of the equal-weight portfolio of the --topk "
+                        "stocks by predictive mean: <stem>_risk.csv (mean, "
+                        "factor and "
+                        "specific variance, vol per day) and "
+                        "<stem>_risk_factors.csv (exposure and variance per "
+                        "day and factor)")
+    p.add_argument("--risk_weights", type=str, default=None,
+                   choices=["minvar", "mv"],
+                   help="with --risk: also write <stem>_weights.csv, the "
+                        "minimum-variance or mean-variance weights of every "
+                        "day's stocks under the model's covariance")
     p.add_argument("--topk", type=int, default=50)
     p.add_argument("--n_drop", type=int, default=10)
     return p
@@ -182,8 +195,88 @@ def range_factors(model, loader, seq_length: int, engine: str = "auto",
     return factors, daily
 
 
+def range_risk(model, loader, seq_length: int, scores, engine: str = "auto",
+               topk: int = 50, risk_weights=None, panel: bool = False):
+    """The factor risk model (factorvae_amd.risk) of every day of the
+    loader for the equal-weight portfolio of the topk stocks by predictive
+    mean, taken from the `mu` column of `scores` (the frame
+    generate_prediction_scores returned for this loader, in its row
+    order): (risk, factors, weights) DataFrames —
+      risk:    one row per day: datetime, n_stocks, mean, mean_factor,
+               var_factor, var_specific, vol;
+      factors: one row per (day, factor): datetime, factor, exposure,
+               factor_var;
+      weights: None, or with risk_weights in ("minvar", "mv") one row per
+               (day, stock): datetime, instrument, weight.
+    The fused engine's risk_many on a GPU (engine "auto"/"fused"),
+    risk.risk_days_eager on the eager module otherwise; panel=True takes
+    the days from a PanelDays."""
+    from .engine.trainer import resolve_engine
+    from .risk import STAT_KEYS, risk_days_eager
+
+    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    model.to(device)
+    hidden = model.feature_extractor.gru.hidden_size
+    fused = resolve_engine(engine, hidden, device.type, warn=False) == "fused"
+    index = loader.dataset.get_index()
+    mu_all = torch.as_tensor(scores["mu"].to_numpy())
+    days, dates, spans, row = [], [], [], 0
+    for char_with_label, _ in loader:
+        n = int(char_with_label.shape[0])
+        if char_with_label.shape[1] == seq_length and n > 0:
+            days.append(char_with_label[:, :, :-1].float())
+            dates.append(index[row][0])
+            spans.append((row, n))
+        row += n
+    if panel:
+        # the loader's days, held once per (stock, date) row
+        pdays = PanelDays.from_loader(loader)
+        days = pdays if fused else [pdays.windows(d)[0]
+                                    for d in range(len(pdays))]
+    weights = []
+    for r0, n in spans:
+        k = max(1, min(int(topk), n))
+        w = torch.zeros(n)
+        w[torch.topk(mu_all[r0:r0 + n], k).indices] = 1.0 / k
+        weights.append(w)
+    solve = (risk_weights,) if risk_weights else ()
+    if fused:
+        from .engine.fused import FusedTrainer
+
+        trainer = FusedTrainer(model, lr=0.0, t_max=1, device=device,
+                               train=False)
+        r = trainer.risk_many(days, weights=weights, solve=solve)
+    else:
+        r = risk_days_eager(model, days, weights=weights, solve=solve)
+    D = len(dates)
+    K = r["exposure"].shape[1] if D else 0
+    risk = pd.DataFrame({
+        "datetime": dates, "n_stocks": r["n"].numpy(),
+        **{k: r[k].numpy() for k in STAT_KEYS}})
+    factors = pd.DataFrame({
+        "datetime": [d for d in dates for _ in range(K)],
+        "factor": list(range(K)) * D,
+        "exposure": r["exposure"].reshape(-1).numpy(),
+        "factor_var": r["factor_var"].reshape(-1).numpy()})
+    wdf = None
+    if risk_weights:
+        rows = [index[i] for r0, n in spans for i in range(r0, r0 + n)]
+        wdf = pd.DataFrame({
+            "datetime": [t[0] for t in rows],
+            "instrument": [t[1] for t in rows],
+            "weight": (torch.cat(r[risk_weights]).numpy() if D
+                       else torch.empty(0).numpy())})
+    return risk, factors, wdf
+
+
 def main(argv=None):
-    args = build_argparser().parse_args(argv)
+    parser = build_argparser()
+    args = parser.parse_args(argv)
+    if args.risk and not args.dist:
+        parser.error("--risk needs --dist (the portfolio is built from the "
+                     "predictive mean)")
+    if args.risk_weights and not args.risk:
+        parser.error("--risk_weights needs --risk")
     targs = test_args(
         run_name=args.run_name, num_factor=args.num_factor,
         hidden_size=args.hidden_size, num_latent=args.num_latent,
@@ -233,6 +326,20 @@ def main(argv=None):
         daily.to_csv(stem + "_daily.csv", index=False)
         print(f"wrote {stem}_factors.csv ({len(factors)} rows) and "
               f"{stem}_daily.csv ({len(daily)} days)")
+
+    if args.risk:
+        risk, rfac, wdf = range_risk(model, loader, args.seq_length, scores,
+                                     engine=args.engine, topk=args.topk,
+                                     risk_weights=args.risk_weights,
+                                     panel=args.panel)
+        stem = os.path.splitext(out_csv)[0]
+        risk.to_csv(stem + "_risk.csv", index=False)
+        rfac.to_csv(stem + "_risk_factors.csv", index=False)
+        print(f"wrote {stem}_risk.csv ({len(risk)} days) and "
+              f"{stem}_risk_factors.csv ({len(rfac)} rows)")
+        if wdf is not None:
+            wdf.to_csv(stem + "_weights.csv", index=False)
+            print(f"wrote {stem}_weights.csv ({len(wdf)} rows)")
 
     if args.backtest:
         merged = scores.join(df[["LABEL0"]], how="inner")

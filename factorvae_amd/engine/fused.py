@@ -160,6 +160,25 @@ class FusedTrainer:
                            and self.H <= 64 and self.K <= 128
                            and os.environ.get("FV_MID_CHAIN", "1") != "0")
         self._chain_pending = False
+        # where the middle chain applies: the fused middle (docs/KERNELS.md).
+        # Main runs gru_fwd -> mid_fwd -> mid_bwd -> enc_bwd_mid -> gru_bwd
+        # with nothing to join: the attention and encoder forwards are one
+        # launch, the attention backward and dec_fwd_bwd are one launch, and
+        # in fp32 dh_combine is gru_bwd's prologue (bit-identical);
+        # FV_MID_FUSE=0 restores the two-stream middle chain.
+        self._mid_fuse = (self._mid_chain
+                          and os.environ.get("FV_MID_FUSE", "1") != "0")
+        self._fuse_pending = False
+        # with the fused middle, in a captured step: the eps / dropout-mask
+        # fills run on side stream 0 in front of attn_qk_fwd instead of at
+        # the head of main. mid_fwd already waits for that stream, so no
+        # edge is added, and the generator calls keep their order (same
+        # draws). FV_RNG_SIDE=0 keeps them on main.
+        self._rng_side = (self._mid_fuse
+                          and os.environ.get("FV_RNG_SIDE", "1") != "0")
+        self._rng_pending = False
+        # whether the last fp32 backward ran dh_combine as gru_bwd's prologue
+        self._combine_ran = False
         if self.bf16:
             C3 = 3 * self.H
             # padded (+ transposed-padded) weight shadows for the
@@ -555,8 +574,18 @@ class FusedTrainer:
         # the K-head query/key projection depends only on parameters:
         # issue it on the side stream overlapped with the extractor
         self._fork(0)
+        fuse = (train and with_loss and self._mid_fuse and N <= 384)
+        e_qk = None
         with self._OnSide(self, 0):
+            if self._rng_pending:
+                # FV_RNG_SIDE: main waits for e_qk below before anything
+                # reads eps or mask
+                self._rng_pending = False
+                self._fill_rng(N)
             ext.attn_qk_fwd(self.p_q, self.p_Wk, self.p_bk, w["qk"], w["cb"])
+            if fuse:
+                e_qk = torch.cuda.Event()
+                e_qk.record(torch.cuda.current_stream(self.device))
 
         if self.fp8:
             # fwd in e4m3 (weights+activations); also emits the bf16
@@ -627,6 +656,25 @@ class FusedTrainer:
         # the posterior-decoded recon
         mask = w["mask"] if self.training else None
         keep_inv = 1.0 / (1.0 - self.DROPOUT_P)
+        if fuse:
+            # the fused middle: both forwards in ONE launch on main, as
+            # gru_fwd's first successor; qk / cb come from side stream 0.
+            # An unsupported shape launches nothing and returns False: the
+            # two kernels below run instead.
+            torch.cuda.current_stream(self.device).wait_event(e_qk)
+            if ext.mid_fwd(w["h"], w["qk"], w["cb"], mask, self.p_Wv,
+                           self.p_bv, p("Wl"), p("bl"), p("wmu_p"),
+                           p("bmu_p"), p("wsig_p"), p("bsig_p"), w["a_att"],
+                           w["sd"], w["guard"], w["u"], w["ctx"], w["hm2"],
+                           w["pmu"], w["psig_pre"], w["psig"], w["psig_c"],
+                           p("Wenc"), p("benc"), yv, w["scores_enc"],
+                           w["a_enc"], w["yp"], p("Wmu_e"), p("bmu_e"),
+                           p("Wsig_e"), p("bsig_e"), w["fmu"], w["fsig_pre"],
+                           w["fsig"], w["fsig_c"], w["enc_done"], alpha,
+                           keep_inv):
+                self._chain_pending = True
+                self._fuse_pending = True
+                return
         self._fork(0)
         with self._OnSide(self, 0):
             if N <= 448:
@@ -723,6 +771,39 @@ class FusedTrainer:
         gWk = self._gstack("Wk.0", (K, H, H))
         gbk = self._gstack("bk.0", (K, H))
         chain, self._chain_pending = self._chain_pending, False
+        fused, self._fuse_pending = self._fuse_pending, False
+        if fused and self._launch_mid_fused(
+                N, yv, mask, alpha, keep_inv, (gWv, gbv, gq, gWk, gbk)):
+            # everything dh needs is on main. In fp32 the three dh terms
+            # are added by gru_bwd itself (its binding says whether that
+            # route exists for this shape); bf16 / fp8 keep dh_combine.
+            combine = not self.bf16
+            if not combine:
+                self._dh_combine()
+            e_encb = torch.cuda.Event()
+            e_encb.record(main)
+
+            def wenc_wgrad():
+                # needed by Adam only; waits for enc_bwd_mid's dscores
+                s0 = sides[0]
+                s0.wait_event(e_encb)
+                with torch.cuda.stream(s0):
+                    ext.gemm_tn(w["dscores"], w["h"], g("Wenc"),
+                                w["tn_part_s"], 2, False, g("benc"),
+                                w["tn_partb_s"], variant=self._gv)
+
+            if comm_overlap:
+                # the reduce below takes Wenc's gradient too
+                wenc_wgrad()
+                wenc_wgrad = None
+            self._comm_overlap_point(main, sides, comm_overlap)
+            # otherwise gru_bwd is enqueued first, as enc_bwd_mid's first
+            # successor, and the Wenc weight gradient behind it
+            self._launch_extractor_bwd(N, T, x2d, chunks, main, sides,
+                                       comm_overlap, combine=combine,
+                                       after_gru=wenc_wgrad,
+                                       ts=1 if self.bf16 else 0)
+            return
         if chain:
             # dh_combine waits for the attention kernel only; the final
             # join before Adam covers what follows it on that stream
@@ -734,9 +815,17 @@ class FusedTrainer:
             self._join(1)
         # ---- attention branch joined; assemble all three dh contributions
         # (attention ds@qk + a@du, encoder dscores@Wenc) in ONE kernel
-        ext.dh_combine(w["dh"], w["ds"], w["qk"], w["a_att"], w["du"],
-                       w["dscores"], p("Wenc"))
+        self._dh_combine()
+        self._comm_overlap_point(main, sides, comm_overlap)
+        self._launch_extractor_bwd(N, T, x2d, chunks, main, sides,
+                                   comm_overlap)
 
+    def _dh_combine(self):
+        ext, w = self.ext, self.ws
+        ext.dh_combine(w["dh"], w["ds"], w["qk"], w["a_att"], w["du"],
+                       w["dscores"], self.p("Wenc"))
+
+    def _comm_overlap_point(self, main, sides, comm_overlap):
         if comm_overlap:
             # every non-extractor gradient (arena tail from Wenc on) is
             # final: reduce it now, overlapped with the extractor bwd
@@ -755,8 +844,54 @@ class FusedTrainer:
                 tail.div_(get_world_size())
                 torch.distributed.all_reduce(tail)
 
-        self._launch_extractor_bwd(N, T, x2d, chunks, main, sides,
-                                   comm_overlap)
+    def _launch_mid_fused(self, N, yv, mask, alpha, keep_inv, gatt):
+        """The fused middle (docs/KERNELS.md): _launch_forward ended behind
+        mid_fwd on main. mid_bwd (attention backward + dec_fwd_bwd, one
+        launch) and enc_bwd_mid follow there, each its predecessor's
+        first-enqueued successor. What only Adam or the caller needs is
+        forked behind mid_bwd onto side stream 0 and enqueued after
+        enc_bwd_mid: two concurrent branches, and nothing main waits for.
+        Returns False, having launched nothing, if mid_bwd refuses the
+        shape; _launch_mid_chain then runs behind mid_fwd."""
+        ext, w, p, g = self.ext, self.ws, self.p, self.g
+        gWv, gbv, gq, gWk, gbk = gatt
+        main = torch.cuda.current_stream(self.device)
+        s0 = self._streams()[0]
+        if not ext.mid_bwd(
+                w["psig"], w["psig_pre"], w["hm2"], p("wmu_p"), p("wsig_p"),
+                p("Wl"), w["h"], w["a_att"], w["sd"], mask, w["guard"],
+                w["u"], self.p_Wv, self.p_q, self.p_Wk, self.p_bk, w["dz2"],
+                w["du"], w["ds"], w["dc"], gWv, gbv, gq, gWk, gbk,
+                w["hpart"], w["fmu"], w["fsig_c"], w["pmu"], w["psig_c"],
+                w["dpmu"], w["dpsig_c"], p("W1d"), p("b1d"), p("wmu_d"),
+                p("bmu_d"), p("wsig_d"), p("bsig_d"), p("Wb"), p("bb"),
+                w["eps"], yv, w["recon"], w["a1"], w["beta"],
+                w["asig_pre"], w["sigma"], w["drecon"], w["dh"], w["dz1"],
+                w["dbeta"], w["dec_part"], alpha, keep_inv, 1.0):
+            return False
+        e_mb = torch.cuda.Event()
+        e_mb.record(main)
+        ext.enc_bwd_mid(w["dec_part"], ext.dec_nblk(N), w["fmu"],
+                        w["fsig_c"], w["pmu"],
+                        w["psig_c"], w["fsig"], w["fsig_pre"], w["yp"],
+                        p("Wmu_e"), p("Wsig_e"), w["a_enc"], yv,
+                        w["dscores"], g("Wmu_e"), g("bmu_e"), g("Wsig_e"),
+                        g("bsig_e"), w["dfmu"], w["dfsig_c"], 1.0)
+        s0.wait_event(e_mb)
+        with torch.cuda.stream(s0):
+            ext.pred_head_reduce(w["hpart"], g("wmu_p"), g("bmu_p"),
+                                 g("wsig_p"), g("bsig_p"), self.K, self.H)
+            ext.gemm_tn(w["dz2"], w["ctx"], g("Wl"), None, 1, False, g("bl"),
+                        variant=self._gv)
+            ext.dec_bwd_reduce_heads(w["dec_part"], g("wmu_d"), g("bmu_d"),
+                                     g("wsig_d"), g("bsig_d"), N, self.K)
+            ext.gemm_tn(w["dz1"], w["h"], g("W1d"), w["tn_part_s"], 2, False,
+                        g("b1d"), w["tn_partb_s"], variant=self._gv)
+            ext.gemm_tn(w["dbeta"], w["h"], g("Wb"), w["tn_part_s"], 2, False,
+                        g("bb"), w["tn_partb_s"], variant=self._gv)
+            ext.loss_scalars(w["recon"], yv, w["fmu"], w["fsig_c"], w["pmu"],
+                             w["psig_c"], w["loss"], w["mse"], w["kl"])
+        return True
 
     def _launch_mid_chain(self, N, yv, mask, alpha, keep_inv, gatt):
         """The middle of the training step as two critical-path nodes,
@@ -899,8 +1034,18 @@ class FusedTrainer:
                         False, g("benc"), w["tn_partb_s"], variant=self._gv)
 
     def _launch_extractor_bwd(self, N, T, x2d, chunks, main, sides,
-                              comm_overlap):
-        """GRU + projections + LayerNorm backward, and the final join."""
+                              comm_overlap, combine=False, after_gru=None,
+                              ts=1):
+        """GRU + projections + LayerNorm backward, and the final join.
+        combine (fp32): w["dh"] is the decoder's, and gru_bwd is asked to
+        add dh_combine's three terms itself. after_gru: enqueues side work
+        that must not be gru_bwd's predecessor's first successor. ts: the
+        side stream of the weight gradients. In fp32 the fused middle
+        passes 0, the stream its own Adam-only work is on: as a branch of
+        its own next to side stream 1 that work shared a hardware queue
+        with the tail's weight gradients and ran behind them, in front of
+        Adam, and the step was 9 % slower than the parent. In bf16 the same
+        move measured slower, so bf16 / fp8 keep 1 (profiles/mid_fuse.md)."""
         ext, w, p, g = self.ext, self.ws, self.p, self.g
         H, R = self.H, N * T
         fork, _on_side = self._fork, self._OnSide
@@ -936,11 +1081,29 @@ class FusedTrainer:
                         w["dgi_bf"].view(N, T, 3 * H),
                         w["dgh_bf"].view(N, T, 3 * H))
         else:
-            ext.gru_bwd(w["dh"], w["h_prev"], w["gates4"], p("Whh"),
-                        w["dgi"], w["dgh"], N, T, H, variant=self._gru_v)
+            # with the operands gru_bwd either runs dh_combine as its
+            # prologue or launches nothing and returns False
+            self._combine_ran = bool(combine and ext.gru_bwd(
+                w["dh"], w["h_prev"], w["gates4"], p("Whh"), w["dgi"],
+                w["dgh"], N, T, H, variant=self._gru_v, ds=w["ds"],
+                qk=w["qk"], a=w["a_att"], du=w["du"],
+                dscores=w["dscores"], Wenc=p("Wenc")))
+            if not self._combine_ran:
+                if combine:
+                    self._dh_combine()
+                ext.gru_bwd(w["dh"], w["h_prev"], w["gates4"], p("Whh"),
+                            w["dgi"], w["dgh"], N, T, H,
+                            variant=self._gru_v)
+        if after_gru is not None:
+            after_gru()
         if self.bf16:
-            fork(1)
-            with _on_side(self, 1):
+            # bf16 / fp8 always pass ts = 1: without the fused Whh weight
+            # gradient, _launch_forward cast h_prev to h_prev_bf on that
+            # stream, and the stream's order is what puts the cast in front
+            # of its consumer below
+            assert ts == 1
+            fork(ts)
+            with _on_side(self, ts):
                 if self._whh_fused:
                     ext.wgrad_reduce(w["whh_part"], g("Whh"),
                                      w["bhh_part"], g("bhh"),
@@ -971,8 +1134,8 @@ class FusedTrainer:
                 ext.gemm_nt_bf16_rs(w["dgi_bf"].view(R, 3 * H), self.wihT_p,
                                     None, None, w["dzx_bf"], w["xp_bf"],
                                     1.0, False)
-            fork(1)
-            with _on_side(self, 1):
+            fork(ts)
+            with _on_side(self, ts):
                 ext.gemm_tn_bf16(w["dzx_bf"], w["xln_bf"], g("W1x"),
                                  w["tn_part3"], chunks, False, g("b1x"),
                                  w["tn_partb3"])
@@ -997,11 +1160,11 @@ class FusedTrainer:
             # their slices to ONE reduce at the end of side 1, and the dxln
             # GEMM forms ln_bwd_params' partials in its epilogue
             one_reduce = bool(self._gv) and self._f32_tail != 2
-            fork(1)
+            fork(ts)
             ext.gemm_nn(w["dgi"].view(R, 3 * H), p("Wih"), None, w["dzx"],
                         1.0, False, False, lrelu_bwd_of=w["xp"],
                         variant=self._gv)
-            with _on_side(self, 1):
+            with _on_side(self, ts):
                 ext.gemm_tn_pair(w["dgh"].view(R, 3 * H),
                                  w["h_prev"].view(R, H), g("Whh"),
                                  w["dgi"].view(R, 3 * H), w["xp"], g("Wih"),
@@ -1025,7 +1188,7 @@ class FusedTrainer:
                 # BEHIND it on the same hardware queue: pair last, step
                 # 4 % slower), the dxln GEMM and the LayerNorm parameter
                 # gradients stay on main's queue
-                fork(1)
+                fork(ts)
                 ln_fused = bool(self._gv) and ext.gemm_nn_ln(
                     w["dzx"], p("W1x"), x2d, w["mean"], w["rstd"],
                     w["ln_part"])
@@ -1034,7 +1197,7 @@ class FusedTrainer:
                     # the GEMM's 64-row tiles at this R
                     ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0,
                                 False, False, variant=self._gv)
-                with _on_side(self, 1):
+                with _on_side(self, ts):
                     ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"],
                                 chunks, False, g("b1x"), w["tn_partb3"],
                                 variant=self._gv, reduce=not one_reduce)
@@ -1053,8 +1216,8 @@ class FusedTrainer:
                                       w["ln_part"], g("ln_g"), g("ln_b"),
                                       chunks)
         else:
-            fork(1)
-            with _on_side(self, 1):
+            fork(ts)
+            with _on_side(self, ts):
                 ext.gemm_tn(w["dgh"].view(R, 3 * H), w["h_prev"].view(R, H),
                             g("Whh"), w["tn_part"], chunks, False,
                             g("bhh"), w["tn_partb"], variant=self._gv)
@@ -1064,8 +1227,8 @@ class FusedTrainer:
             ext.gemm_nn(w["dgi"].view(R, 3 * H), p("Wih"), None, w["dxp"], 1.0,
                         False, False, variant=self._gv)
             ext.lrelu_bwd(w["dxp"], w["xp"], w["dzx"])
-            fork(1)
-            with _on_side(self, 1):
+            fork(ts)
+            with _on_side(self, ts):
                 ext.gemm_tn(w["dzx"], w["xln"], g("W1x"), w["tn_part3"], chunks,
                             False, g("b1x"), w["tn_partb3"], variant=self._gv)
             ext.gemm_nn(w["dzx"], p("W1x"), None, w["dxln"], 1.0, False, False,
@@ -1276,8 +1439,14 @@ class FusedTrainer:
                 self.ext.step_inc(self.step_t)
             inc_early = True
         if rng_in_graph:
-            self._fill_rng(N)
+            if self._rng_side and N <= 384:
+                # _launch_forward takes its fused path and issues the fills
+                # on side stream 0
+                self._rng_pending = True
+            else:
+                self._fill_rng(N)
         self._launch_forward(N, T, x=x, y=y, train=True)
+        assert not self._rng_pending
         self._launch_backward(N, T, x=x, y=y, comm_overlap=comm_in_graph)
         if comm_in_graph:
             # the non-extractor slice was reduced inside backward,

@@ -606,19 +606,50 @@ void gru_fwd(Tensor gi, Tensor Whh, Tensor bhh, Tensor h_final,
                  cur_stream()));
 }
 
-void gru_bwd(Tensor dh_final, Tensor h_prev, Tensor gates4, Tensor Whh,
+// With the six dh_combine operands (ds / a (N,K), qk / du (K,H), dscores
+// (N,M), Wenc (M,H)) dh_final is the decoder's dh, and the kernel forms
+// dh_combine's sum itself and leaves it in dh_final. That exists on the
+// wave route only (H = 64, N <= gru_wave_max_n(), fp32 outputs, variant 1):
+// returns true when it ran that way. With the operands and off that route
+// it launches NOTHING and returns false; the caller runs dh_combine and
+// calls again without them. Without the operands it returns false.
+bool gru_bwd(Tensor dh_final, Tensor h_prev, Tensor gates4, Tensor Whh,
              Tensor dgi, Tensor dgh, long N, long T, long H,
              OptTensor dgi_bf = c10::nullopt,
-             OptTensor dgh_bf = c10::nullopt, long variant = 1) {
+             OptTensor dgh_bf = c10::nullopt, long variant = 1,
+             OptTensor ds = c10::nullopt, OptTensor qk = c10::nullopt,
+             OptTensor a = c10::nullopt, OptTensor du = c10::nullopt,
+             OptTensor dscores = c10::nullopt,
+             OptTensor Wenc = c10::nullopt) {
   OP("gru_bwd", dh_final);
   NUM(N); NUM(T); NUM(H);
   op.require(variant == 0 || variant == 1, "variant = ", variant,
              ", must be 0 or 1");
   const long G = N * T * 3 * H;
+  const bool comb = ds.has_value();
+  op.require(comb == qk.has_value() && comb == a.has_value() &&
+                 comb == du.has_value() && comb == dscores.has_value() &&
+                 comb == Wenc.has_value(),
+             "ds, qk, a, du, dscores, Wenc come as a set of six");
+  if (comb) {
+    if (dgi_bf.has_value() || dgh_bf.has_value()) return false;
+    const long K = op.dim(*qk, "qk", 0), M = op.dim(*Wenc, "Wenc", 0);
+    op.require(op.dim(*qk, "qk", 1) == H && op.dim(*Wenc, "Wenc", 1) == H,
+               "qk / Wenc must have H columns");
+    int fused = 0;
+    RUN(fv_gru_bwd_combine(
+        P_F32(dh_final, N * H), P_F32(ds, N * K), P_F32(qk, K * H),
+        P_F32(a, N * K), P_F32(du, K * H), P_F32(dscores, N * M),
+        P_F32_EQ(Wenc, M * H), K, M, P_F32(h_prev, N * T * H),
+        P_F32(gates4, N * T * 4 * H), P_F32_EQ(Whh, 3 * H * H), P_F32(dgi, G),
+        P_F32(dgh, G), N, T, H, (int)variant, &fused, cur_stream()));
+    return fused != 0;
+  }
   RUN(fv_gru_bwd(P_F32(dh_final, N * H), P_F32(h_prev, N * T * H),
                  P_F32(gates4, N * T * 4 * H), P_F32_EQ(Whh, 3 * H * H),
                  P_F32(dgi, G), P_F32(dgh, G), P_BF16(dgi_bf, G),
                  P_BF16(dgh_bf, G), N, T, H, (int)variant, cur_stream()));
+  return false;
 }
 
 void gru_fwd_mfma(Tensor gi, Tensor whh_bf, Tensor bhh, Tensor h_final,
@@ -1079,6 +1110,95 @@ void dec_bwd_reduce_heads(Tensor part, Tensor dwmu, Tensor dbmu,
       cur_stream()));
 }
 
+// ---- the fused middle (docs/KERNELS.md): attn_fused_fwd + enc_fused_fwd
+// (with the heads) as one launch, argument for argument. Returns false,
+// launching nothing, outside mid_fuse.hip's limits.
+bool mid_fwd(Tensor h, Tensor qk, Tensor cb, OptTensor mask, Tensor Wv,
+             Tensor bv, Tensor Wl, Tensor bl, Tensor wmu, Tensor bmu,
+             Tensor wsig, Tensor bsig, Tensor a, Tensor sd, Tensor guard,
+             Tensor u, Tensor ctx, Tensor hm2, Tensor pmu, Tensor psig_pre,
+             Tensor psig, Tensor psig_c, Tensor Wenc, Tensor benc, Tensor y,
+             Tensor scores, Tensor a_enc, Tensor yp, Tensor Wmu_e,
+             Tensor bmu_e, Tensor Wsig_e, Tensor bsig_e, Tensor fmu,
+             Tensor fsig_pre, Tensor fsig, Tensor fsig_c, Tensor done,
+             double alpha, double keep_inv) {
+  OP("mid_fwd", h);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(qk, 0), M = DIM(Wenc, 0);
+  op.require(DIM(qk, 1) == H, "qk must be (K,H)");
+  op.require(DIM(Wenc, 1) == H, "Wenc must be (M,H)");
+  int ran = 0;
+  RUN(fv_mid_fwd(
+      P_F32(h, N * H), P_F32_EQ(qk, K * H), P_F32_EQ(cb, K),
+      P_F32(mask, N * K), P_F32_EQ(Wv, K * H * H), P_F32_EQ(bv, K * H),
+      P_F32_EQ(Wl, H * H), P_F32_EQ(bl, H), P_F32_EQ(wmu, H),
+      P_F32_EQ(bmu, 1), P_F32_EQ(wsig, H), P_F32_EQ(bsig, 1),
+      P_F32(a, N * K), P_F32(sd, N * K), P_I32(guard, K), P_F32(u, K * H),
+      P_F32(ctx, K * H), P_F32(hm2, K * H), P_F32(pmu, K),
+      P_F32(psig_pre, K), P_F32(psig, K), P_F32(psig_c, K),
+      P_F32_EQ(Wenc, M * H), P_F32_EQ(benc, M), P_F32(y, N),
+      P_F32(scores, N * M), P_F32(a_enc, N * M), P_F32(yp, M),
+      P_F32_EQ(Wmu_e, K * M), P_F32_EQ(bmu_e, K), P_F32_EQ(Wsig_e, K * M),
+      P_F32_EQ(bsig_e, K), P_F32(fmu, K), P_F32(fsig_pre, K), P_F32(fsig, K),
+      P_F32(fsig_c, K), P_I32(done, 1), N, K, M, H, (float)alpha,
+      (float)keep_inv, &ran, cur_stream()));
+  return ran != 0;
+}
+
+// attn_fused_bwd in its KL-gradient form (dpmu / dpsig_c are outputs) +
+// dec_fwd_bwd as one launch. It does NOT run pred_head_reduce: hpart is
+// left for the caller's pred_head_reduce. Returns false, launching
+// nothing, outside mid_fuse.hip's limits.
+bool mid_bwd(Tensor psig, Tensor psig_pre, Tensor hm2, Tensor wmu,
+             Tensor wsig, Tensor Wl, Tensor h, Tensor a, Tensor sd,
+             OptTensor mask, Tensor guard, Tensor u, Tensor Wv, Tensor q,
+             Tensor Wk, Tensor bk, Tensor dz2, Tensor du, Tensor ds,
+             Tensor dc, Tensor dWv, Tensor dbv, Tensor dq, Tensor dWk,
+             Tensor dbk, Tensor hpart, Tensor fmu, Tensor fsig_c, Tensor pmu,
+             Tensor psig_c, Tensor dpmu, Tensor dpsig_c, Tensor W1, Tensor b1,
+             Tensor wmu_d, Tensor bmu_d, Tensor wsig_d, Tensor bsig_d,
+             Tensor Wb, Tensor bb, Tensor eps, Tensor y, Tensor recon,
+             Tensor a1, Tensor beta, Tensor asig_pre, Tensor sigma,
+             Tensor drecon, Tensor dh, Tensor dz1, Tensor dbeta, Tensor part,
+             double alpha, double keep_inv, double gscale) {
+  OP("mid_bwd", psig);
+  const long N = DIM(h, 0), H = DIM(h, 1), K = DIM(q, 0);
+  op.require(DIM(q, 1) == H, "q must be (K,H)");
+  op.require(DIM(Wb, 0) == K && DIM(Wb, 1) == H, "Wb must be (K,H)");
+  op.require(N >= 1, "h has no rows");
+  int ran = 0;
+  RUN(fv_mid_bwd(
+      P_F32(psig, K), P_F32(psig_pre, K), P_F32(hm2, K * H),
+      P_F32_EQ(wmu, H), P_F32_EQ(wsig, H), P_F32_EQ(Wl, H * H),
+      P_F32(h, N * H), P_F32(a, N * K), P_F32(sd, N * K), P_F32(mask, N * K),
+      P_I32(guard, K), P_F32(u, K * H), P_F32_EQ(Wv, K * H * H),
+      P_F32_EQ(q, K * H), P_F32_EQ(Wk, K * H * H), P_F32_EQ(bk, K * H),
+      P_F32(dz2, K * H), P_F32(du, K * H), P_F32(ds, N * K), P_F32(dc, K),
+      P_F32_EQ(dWv, K * H * H), P_F32_EQ(dbv, K * H), P_F32_EQ(dq, K * H),
+      P_F32_EQ(dWk, K * H * H), P_F32_EQ(dbk, K * H),
+      P_F32(hpart, K * (2 * H + 2)), P_F32(fmu, K), P_F32(fsig_c, K),
+      P_F32(pmu, K), P_F32(psig_c, K), P_F32(dpmu, K), P_F32(dpsig_c, K),
+      P_F32_EQ(W1, H * H), P_F32(b1, H), P_F32(wmu_d, H), P_F32(bmu_d, 1),
+      P_F32(wsig_d, H), P_F32(bsig_d, 1), P_F32_EQ(Wb, K * H), P_F32(bb, K),
+      P_F32(eps, N), P_F32(y, N), P_F32(recon, N), P_F32(a1, N * H),
+      P_F32(beta, N * K), P_F32(asig_pre, N), P_F32(sigma, N),
+      P_F32(drecon, N), P_F32(dh, N * H), P_F32(dz1, N * H),
+      P_F32(dbeta, N * K),
+      P_F32(part, fv_dec_nblk(N) * (2 * K + 2 * H + 2)), N, K, H,
+      (float)alpha, (float)keep_inv, (float)gscale, &ran, cur_stream()));
+  return ran != 0;
+}
+
+// the (2H + 2) predictor head gradients out of hpart, K * (2H + 2) floats
+void pred_head_reduce(Tensor hpart, Tensor dwmu, Tensor dbmu, Tensor dwsig,
+                      Tensor dbsig, long K, long H) {
+  OP("pred_head_reduce", hpart);
+  NUM(K); NUM(H);
+  op.require(K >= 1 && H >= 1, "needs K >= 1 and H >= 1");
+  RUN(fv_pred_head_reduce(P_F32(hpart, K * (2 * H + 2)), P_F32_EQ(dwmu, H),
+                          P_F32_EQ(dbmu, 1), P_F32_EQ(dwsig, H),
+                          P_F32_EQ(dbsig, 1), K, H, cur_stream()));
+}
+
 // ----------------------------------------------------------------- loss
 // recon / y / drecon hold N floats, the KL inputs and gradients K each
 void loss_fused(Tensor recon, Tensor y, Tensor fmu, Tensor fsig_c, Tensor pmu,
@@ -1425,7 +1545,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("gates4"), py::arg("Whh"), py::arg("dgi"), py::arg("dgh"),
           py::arg("N"), py::arg("T"), py::arg("H"),
           py::arg("dgi_bf") = py::none(), py::arg("dgh_bf") = py::none(),
-          py::arg("variant") = 1);
+          py::arg("variant") = 1, py::arg("ds") = py::none(),
+          py::arg("qk") = py::none(), py::arg("a") = py::none(),
+          py::arg("du") = py::none(), py::arg("dscores") = py::none(),
+          py::arg("Wenc") = py::none());
+  mod.def("mid_fwd", &mid_fwd);
+  mod.def("mid_bwd", &mid_bwd);
+  mod.def("pred_head_reduce", &pred_head_reduce);
   mod.def("enc_softmax_fwd", &enc_softmax_fwd);
   mod.def("enc_softmax_bwd", &enc_softmax_bwd);
   mod.def("enc_heads_fwd", &enc_heads_fwd);

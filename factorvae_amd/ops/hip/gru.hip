@@ -527,4 +527,23 @@ hipError_t fv_gru_bwd(const float* dh_final, const float* h_prev,
   return hipSuccess;
 }
 
+// fv_dh_combine followed by fv_gru_bwd as one launch, on the wave route
+// only (what use_wave_ accepts; fp32 outputs). *fused = 0 and nothing is
+// launched otherwise: the caller then runs the two launchers.
+hipError_t fv_gru_bwd_combine(float* dh, const float* ds, const float* qk,
+                              const float* a, const float* du,
+                              const float* dscores, const float* Wenc, int K,
+                              int M, const float* h_prev, const float* gates4,
+                              const float* Whh, float* dgi, float* dgh, int N,
+                              int T, int H, int variant, int* fused,
+                              hipStream_t stream) {
+  *fused = 0;
+  if (!use_wave_(variant, N, H)) return hipSuccess;
+  hipError_t e = fv_gru_bwd_wave_f32_combine(dh, ds, qk, a, du, dscores, Wenc,
+                                             K, M, h_prev, gates4, Whh, dgi,
+                                             dgh, N, T, H, stream);
+  if (e == hipSuccess) *fused = 1;
+  return e;
+}
+
 }  // extern "C"

@@ -192,6 +192,24 @@ __global__ __launch_bounds__(256) void gru_fwd_wave_f32_kernel(
   }
 }
 
+// COMBINE (the fused middle, docs/KERNELS.md): dh_combine_kernel as this
+// kernel's prologue. That kernel has this one's mapping, wave <-> stock row
+// and lane <-> H column, and runs one fmaf chain per element from the
+// decoder's dh: over k fmaf(ds[n][k], qk[k][lane], .) then
+// fmaf(a[n][k], du[k][lane], .), over m fmaf(dscores[n][m], Wenc[m][lane], .).
+// The same explicit fmafs in the same order run here, so dh has the same
+// bits. The qk / du / Wenc rows come as coalesced 256-byte rows from L2
+// (dh_combine reads an LDS copy of the same values), the row's ds / a /
+// dscores through wave-uniform addresses. K and M are runtime bounds, so
+// the two loops are unrolled 4 and 8 times and each trip waits for its own
+// eight row loads: only the first trip overlaps the 192 Whh loads, the rest
+// are K/4 + M/8 load round trips in a row (21 at K = 20, M = 128). With the
+// weights holding 192 of the 250 VGPRs there is no room to keep more rows
+// in flight. The prologue therefore costs about as much as dh_combine did
+// (profiles/mid_fuse.md); what it removes is the launch and its join. The
+// combined dh goes back to dh_io, where dh_combine leaves it. Without
+// COMBINE the operands after T are not looked at.
+template <bool COMBINE = false>
 __global__ __launch_bounds__(256) void gru_bwd_wave_f32_kernel(
     const float* __restrict__ dh_final,   // (N,64)
     const float* __restrict__ h_prev_in,  // (N,T,64)
@@ -199,7 +217,15 @@ __global__ __launch_bounds__(256) void gru_bwd_wave_f32_kernel(
     const float* __restrict__ Whh,        // (192,64)
     float* __restrict__ dgi,              // (N,T,192)
     float* __restrict__ dgh,              // (N,T,192)
-    int N, int T) {
+    int N, int T,
+    float* __restrict__ dh_io,            // (N,64) in: decoder's, out: sum
+    const float* __restrict__ ds,         // (N,K)
+    const float* __restrict__ qk,         // (K,64)
+    const float* __restrict__ a,          // (N,K)
+    const float* __restrict__ du,         // (K,64)
+    const float* __restrict__ dscores,    // (N,M)
+    const float* __restrict__ Wenc,       // (M,64)
+    int K, int M) {
   __shared__ __attribute__((aligned(16))) float dgS[GW_WPB][192];
 
   const int tid = threadIdx.x;
@@ -214,7 +240,27 @@ __global__ __launch_bounds__(256) void gru_bwd_wave_f32_kernel(
   for (int k = 0; k < 192; ++k) w[k] = Whh[k * 64 + lane];
 
   const long row = (long)s * T;
-  float dh = dh_final[(long)s * 64 + lane];
+  float dh;
+  if (COMBINE) {
+    // s is the same in every lane of the wave; say so, and the row's
+    // operands are read once per wave
+    const long su = __builtin_amdgcn_readfirstlane(s);
+    const float* dsr = ds + su * K;
+    const float* ar = a + su * K;
+    const float* dr = dscores + su * M;
+    float acc = dh_io[(long)s * 64 + lane];
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      acc = fmaf(dsr[k], qk[k * 64 + lane], acc);
+      acc = fmaf(ar[k], du[k * 64 + lane], acc);
+    }
+#pragma unroll 8
+    for (int m = 0; m < M; ++m) acc = fmaf(dr[m], Wenc[m * 64 + lane], acc);
+    dh_io[(long)s * 64 + lane] = acc;
+    dh = acc;
+  } else {
+    dh = dh_final[(long)s * 64 + lane];
+  }
 
   float pr = 0.f, pz = 0.f, pn = 0.f, pq = 0.f, php = 0.f;
   if (T > 0) {
@@ -337,8 +383,28 @@ hipError_t fv_gru_bwd_wave_f32(const float* dh_final, const float* h_prev,
   if (H != 64) return hipErrorInvalidValue;
   if (N <= 0) return hipSuccess;
   dim3 grid((N + GW_WPB - 1) / GW_WPB);
-  hipLaunchKernelGGL(gru_bwd_wave_f32_kernel, grid, dim3(256), 0, stream,
-                     dh_final, h_prev, gates4, Whh, dgi, dgh, N, T);
+  hipLaunchKernelGGL(gru_bwd_wave_f32_kernel<false>, grid, dim3(256), 0,
+                     stream, dh_final, h_prev, gates4, Whh, dgi, dgh, N, T,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, 0, 0);
+  HIP_CHECK_LAST();
+  return hipSuccess;
+}
+
+hipError_t fv_gru_bwd_wave_f32_combine(float* dh, const float* ds,
+                                       const float* qk, const float* a,
+                                       const float* du, const float* dscores,
+                                       const float* Wenc, int K, int M,
+                                       const float* h_prev,
+                                       const float* gates4, const float* Whh,
+                                       float* dgi, float* dgh, int N, int T,
+                                       int H, hipStream_t stream) {
+  if (H != 64 || K < 0 || M < 0) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  dim3 grid((N + GW_WPB - 1) / GW_WPB);
+  hipLaunchKernelGGL(gru_bwd_wave_f32_kernel<true>, grid, dim3(256), 0,
+                     stream, nullptr, h_prev, gates4, Whh, dgi, dgh, N, T, dh,
+                     ds, qk, a, du, dscores, Wenc, K, M);
   HIP_CHECK_LAST();
   return hipSuccess;
 }

@@ -152,6 +152,15 @@ hipError_t fv_gru_bwd(const float* dh_final, const float* h_prev,
                       const float* gates4, const float* Whh, float* dgi,
                       float* dgh, void* dgi_bf, void* dgh_bf, int N, int T,
                       int H, int variant, hipStream_t stream);
+// fv_dh_combine and fv_gru_bwd in one launch where fv_gru_bwd would take the
+// wave kernel (fp32 outputs); otherwise *fused = 0 and nothing is launched
+hipError_t fv_gru_bwd_combine(float* dh, const float* ds, const float* qk,
+                              const float* a, const float* du,
+                              const float* dscores, const float* Wenc, int K,
+                              int M, const float* h_prev, const float* gates4,
+                              const float* Whh, float* dgi, float* dgh, int N,
+                              int T, int H, int variant, int* fused,
+                              hipStream_t stream);
 // The gather forms of the inference recurrences (gru_gather.h): gi_rows is
 // (U,3H), idx (N,T) int32, and step t of stock n reads row idx[n*T + t]; an
 // index outside [0,U) reads nothing and makes that stock's h_final NaN.
@@ -180,6 +189,14 @@ hipError_t fv_gru_bwd_wave_f32(const float* dh_final, const float* h_prev,
                                const float* gates4, const float* Whh,
                                float* dgi, float* dgh, int N, int T, int H,
                                hipStream_t stream);
+hipError_t fv_gru_bwd_wave_f32_combine(float* dh, const float* ds,
+                                       const float* qk, const float* a,
+                                       const float* du, const float* dscores,
+                                       const float* Wenc, int K, int M,
+                                       const float* h_prev,
+                                       const float* gates4, const float* Whh,
+                                       float* dgi, float* dgh, int N, int T,
+                                       int H, hipStream_t stream);
 
 // ---- gru_mfma.hip -----------------------------------------------------
 // number of workgroups fv_gru_bwd_mfma launches, one wgrad partial each
@@ -281,6 +298,10 @@ hipError_t fv_attn_fused_bwd(const float* dpmu, const float* dpsig_c,
                              const float* kl_fmu, const float* kl_fsig_c,
                              const float* kl_pmu, const float* kl_psig_c,
                              float kl_gscale, hipStream_t s);
+// the reduce fv_attn_fused_bwd / fv_pred_mlp_bwd end with, on its own
+hipError_t fv_pred_head_reduce(const float* hpart, float* dwmu, float* dbmu,
+                               float* dwsig, float* dbsig, int K, int H,
+                               hipStream_t s);
 hipError_t fv_attn_fused_fwd(const float* h, const float* qk, const float* cb,
                              const float* mask, const float* Wv,
                              const float* bv, const float* Wl, const float* bl,
@@ -352,6 +373,39 @@ hipError_t fv_dec_bwd(const float* drecon, const float* h, const float* a1,
                       float* dz1, float* dbeta, float* part, float* dfmu,
                       float* dfsig_c, float* dwmu, float* dbmu, float* dwsig,
                       float* dbsig, int N, int K, int H, hipStream_t s);
+
+// ---- mid_fuse.hip (the fused middle, docs/KERNELS.md) ------------------
+// fv_attn_fused_fwd and fv_enc_fused_fwd (with the heads) as one launch;
+// fv_attn_fused_bwd's kernel (KL-gradient form, without its
+// pred_head_reduce) and fv_dec_fwd_bwd as one launch. Latency-oriented
+// variants only: N <= 384, H <= 64 a multiple of 4, K <= 128, LDS within
+// 160 KiB. Otherwise *ran = 0 and nothing is launched.
+hipError_t fv_mid_fwd(
+    const float* h, const float* qk, const float* cb, const float* mask,
+    const float* Wv, const float* bv, const float* Wl, const float* bl,
+    const float* wmu_p, const float* bmu_p, const float* wsig_p,
+    const float* bsig_p, float* a_att, float* sd, int* guard, float* u,
+    float* ctx, float* hm2, float* pmu, float* psig_pre, float* psig,
+    float* psig_c, const float* Wenc, const float* benc, const float* y,
+    float* scores, float* a_enc, float* yp, const float* Wmu_e,
+    const float* bmu_e, const float* Wsig_e, const float* bsig_e, float* fmu,
+    float* fsig_pre, float* fsig, float* fsig_c, int* done, int N, int K,
+    int M, int H, float alpha, float keep_inv, int* ran, hipStream_t s);
+hipError_t fv_mid_bwd(
+    const float* psig, const float* psig_pre, const float* hm2,
+    const float* wmu_p, const float* wsig_p, const float* Wl, const float* h,
+    const float* a_att, const float* sd, const float* mask, const int* guard,
+    const float* u, const float* Wv, const float* q, const float* Wk,
+    const float* bk, float* dz2, float* du, float* ds, float* dc, float* dWv,
+    float* dbv, float* dq, float* dWk, float* dbk, float* hpart,
+    const float* fmu, const float* fsig_c, const float* pmu,
+    const float* psig_c, float* dpmu, float* dpsig_c, const float* W1,
+    const float* b1, const float* wmu_d, const float* bmu_d,
+    const float* wsig_d, const float* bsig_d, const float* Wb,
+    const float* bb, const float* eps, const float* y, float* recon,
+    float* a1, float* beta, float* asig_pre, float* sigma, float* drecon,
+    float* dh, float* dz1, float* dbeta, float* part, int N, int K, int H,
+    float alpha, float keep_inv, float gscale, int* ran, hipStream_t s);
 
 // ---- loss.hip ---------------------------------------------------------
 hipError_t fv_loss_fused(const float* recon, const float* y, const float* fmu,
